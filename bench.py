@@ -7,8 +7,16 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task description): BASELINE.json's metric
-(training frames/s, frame = one 512x432 image of a 4-frame track), plus
+Prints ONE JSON line on rank 0: BASELINE.json's metric (training frames/s, frame = one 512x432 image of a 4-frame track),
+`ms_per_step` (the mean time of one of the --steps timed steps) and the loss terms of the last step.  A plain run sets up, warms
+up, times the steps and prints that line; nothing else.
+
+  --dump-outputs DIR : after the timed steps, what the last of them gives its caller, as DIR/<name>.npy (float32): the loss
+                 terms, the disparity output and the updated parameters (a fixed, seeded sample of DUMP_MAX_ELEMS entries of
+                 an array larger than that).  Inputs are seeded: the same arguments give the same inputs on every run, so two
+                 builds can be compared output for output: with this option every step trains from the same seeded state (see step()).
+  --full       : everything else the benchmark measures and checks, after the timed steps (the fields are null without it):
+  eager_launch_frames_per_s : the same step launched eagerly;
   roofline     : the dominant kernel (MFMA fp32 32->32 3x3 implicit-GEMM conv) against the fp32 matrix peak,
                  duration measured live with HIP events around every launch of that kernel in one step;
   cpu_baseline : the CPU oracle (pure PyTorch restatement of the reference step) timed on the host cores on a
@@ -16,8 +24,10 @@ Prints ONE JSON line on rank 0 (contract in the task description): BASELINE.json
   disp_l1_vs_ref : mean |disparity(HIP) - disparity(reference)| on that sample's inputs (the metric's "disp L1 vs ref"): the
                  free-running HIP forward against the reference's own 512x432 output (tests/golden/mf_512x432_bs1.npz), with the
                  comparison against the CPU oracle of this host as secondary fields;
-  ranks_seen / devices_seen / replicas_equal : at N > 1 every rank checks the world size, that no two ranks share a
-                 device (RCCL) and, after the timed loop, that all parameter replicas are bit-identical.
+  strict_fp32_frames_per_s / extra_dis_sf : child runs of the step on the three-term bf16 split and of DIS-SF (N = 1 DIS-MF);
+  replicas_equal : at N > 1, after the timed loop, that all parameter replicas are bit-identical.
+ranks_seen / devices_seen: at N > 1 every rank checks the world size and that no two ranks share a device (RCCL), before
+anything is timed (every run).
 """
 import argparse
 import json
@@ -44,6 +54,9 @@ SURVEY_8D_STEP_BYTES_NOTE = 'SURVEY 8(d): convs 3 x 5.65 GB/sample x 4 samples =
 SURVEY_8D_SF_STEP_BYTES = {'f32': 3 * 0.198e9 * 32 + 0.10e9 * 32, 'bf16': 3 * 0.099e9 * 32 + 0.10e9 * 32}
 SURVEY_8D_SF_STEP_BYTES_NOTE = ('SURVEY 8(d): convs 3 x 0.198 GB/image (fp32; 0.099 with bf16 activation storage) x 32 images + per-pixel '
                                 'kernels 0.10 GB/frame x 32')
+# --dump-outputs: at most this many entries per array (2 arrays x 16 MB: DIS-MF's 3.5 M disparities and 0.5 M parameters are
+# written whole, DIS-SF's 7.1 M disparities and 31.6 M parameters are sampled)
+DUMP_MAX_ELEMS = 4 << 20
 
 
 def make_args(bs, arch='multi_frame'):
@@ -65,6 +78,19 @@ def make_device_batch(settings, bs, seed, dev):
             out[k] = torch.from_numpy(v).to(dev)
     out['_flow_stacked'] = torch.from_numpy(stacked).to(dev)
     return out
+
+
+def dump_outputs(path, stepper, opt, disparity):
+    """Write what the last step of `stepper` gives its caller as path/<name>.npy (float32): the loss terms, the disparity
+    output (full resolution) and the updated flat parameter buffer.  An array longer than DUMP_MAX_ELEMS is flattened and
+    sampled at the same sorted indices (numpy default_rng(0)) every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss_terms': stepper.loss_buf[:stepper.nterms], 'disparity': disparity.reshape(-1), 'parameters': opt.flat_p[:opt.n]}
+    for name, t in arrays.items():
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + '.npy'), t.detach().float().cpu().numpy())
 
 
 def conv_flops(n, ho, wo, cin, cout, k):
@@ -294,14 +320,21 @@ def main():
                     help='single_frame only: bf16 = DispNetS with bf16 activation storage (BASELINE config 2; one bf16 product per '
                          'MAC, fp32 accumulate; parameters / disparities / losses fp32), reported under its own label')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of one hipGraph')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other leg: eager-launch timing, the per-call roofline step, the '
+                         'CPU baseline with the disparity comparison against the reference, the child legs and (N > 1) the '
+                         'replica check; the --no-* options below skip single legs of a --full run')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--dump-calls', default=None, help='write the per-call HIP-event times of one eager step to this file')
+    ap.add_argument('--dump-calls', default=None,
+                    help='(--full) write the per-call HIP-event times of one eager step to this file')
     ap.add_argument('--no-eager-leg', action='store_true', help='skip the eager-launch timing of the same step')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'],
                     help='torch.distributed backend for --gpus > 1 (nccl = RCCL over xGMI; gloo only to exercise the '
                          'multi-rank code path on a box with fewer GPUs than ranks)')
     ap.add_argument('--no-extra-legs', action='store_true',
-                    help='the default N = 1 DIS-MF run also times, as fresh child processes after everything of this run has been '
+                    help='the --full N = 1 DIS-MF run also times, as fresh child processes after everything of this run has been '
                          'measured, (1) the same step on the strict three-term bf16 split (DIS_CONV_SPLIT=bf16x3, >= 24-bit operands: '
                          '`strict_fp32_frames_per_s`) and (2) BASELINE config 2, DIS-SF bs=8, with bf16 activation storage and in '
                          'fp32 (`extra_dis_sf`); this flag skips them (profiling runs, child runs)')
@@ -312,6 +345,8 @@ def main():
         args.bs = 4 if args.arch == 'multi_frame' else 8
     if args.dtype == 'bf16' and args.arch != 'single_frame':
         raise SystemExit('--dtype bf16 is the DIS-SF configuration (BASELINE config 2); DIS-MF runs fp32')
+    if args.dump_calls and not args.full:
+        raise SystemExit('--dump-calls records the per-call step of --full: add --full')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # bare `python bench.py --gpus N`: this process never touches a GPU; it starts the N ranks as fresh children
@@ -373,6 +408,17 @@ def main():
     worker.current_epoch = args.epoch
     opt = FlatAdam(net.parameters(), lr=1e-4, world_size=world)
     batch = make_device_batch(settings, args.bs, 1234 + rank, dev)  # weak scaling: own tracks per rank
+    last_out = {}
+    if args.dump_outputs:
+        # the step keeps no reference to its disparity output: hold the forward's (under the captured graph a static buffer
+        # that every replay rewrites, so after the timed loop it is the last step's)
+        net_forward = worker.net_forward
+
+        def net_forward_kept(net_, flow):
+            out = net_forward(net_, flow)
+            last_out['disparity'] = out if mf else out[0]
+            return out
+        worker.net_forward = net_forward_kept
 
     from depthinspace_amd.trainer import GraphedStep
     # the product's own step object: Worker.train_epoch(use_graph=True) runs the same one (trainer.GraphedStep)
@@ -386,7 +432,19 @@ def main():
     def fwd_bwd():  # (roofline leg below)
         stepper._forward_loss().backward()
 
+    # --dump-outputs: every warm-up and timed step trains from the same seeded parameters and Adam moments (the step counter runs
+    # on).  The step's gradient scatters are order-dependent atomics (tests/test_determinism_gpu.py) whose noise compounds over
+    # consecutive Adam steps - after 300 of them the DIS-MF parameters of two runs differ by 2 % - so without the restore the last
+    # step's inputs, and what it computes, would differ from run to run.  The restore is 3 device copies of the flat buffers per
+    # step, which measured 0.3 - 0.5 % of a step (DIS-MF 6 MB, DIS-SF 0.38 GB): a plain run, whose figure is the headline,
+    # trains on without it.
+    state = (opt.flat_p, opt.exp_avg, opt.exp_avg_sq)
+    state0 = [t.clone() for t in state] if args.dump_outputs else None
+
     def step():
+        if state0 is not None:
+            for t, t0 in zip(state, state0):
+                t.copy_(t0)
         stepper.run()
 
     # ---- warm-up (the first graph-mode call runs eager warm-up steps, then captures)
@@ -414,10 +472,12 @@ def main():
     nterms = stepper.nterms
     losses = stepper.losses()
     adam_steps = opt.step_count
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, stepper, opt, last_out['disparity'])   # before any --full leg runs more steps on the same buffers
     # ---- replicas identical after the timed steps: every rank's parameter checksum (fp64 sum and sum of squares of the flat
     # parameter buffer, and its step counter) gathered and compared bit for bit
     replicas_equal = None
-    if world > 1:
+    if world > 1 and args.full:
         ck = torch.stack([opt.flat_p.double().sum(), (opt.flat_p.double() ** 2).sum(),
                           opt.state_dev[0].double()])
         if args.backend != 'nccl':
@@ -429,7 +489,7 @@ def main():
 
     # ---- the same loop launched eagerly (what Worker.train_step does without DIS_TRAIN_GRAPH): reported beside the headline
     eager_fps = None
-    if rank == 0 and world == 1 and use_graph and not args.no_eager_leg:
+    if args.full and rank == 0 and world == 1 and use_graph and not args.no_eager_leg:
         est = GraphedStep(worker, net, opt, batch, use_graph=False)
         for _ in range(2):
             est.run()
@@ -445,7 +505,7 @@ def main():
     roof = None
     hbm = None
     kernel_ms = None
-    if rank == 0:
+    if args.full and rank == 0:
         snap = [t.clone() for t in (opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.state_dev)]
         overlap, opt.overlap = opt.overlap, False   # rank-local leg: the gradient buckets must not start all-reduces here
         lib.profile_start()
@@ -668,7 +728,7 @@ def main():
         kernel_ms = {k: {'calls': v[0], 'ms': round(v[1], 3)} for k, v in top}
     cpu = None
     l1_ref = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # BASELINE metric, second half ("disp L1 vs ref"): the HIP forward on the oracle's bs=1 inputs and initial parameters
         # against the disparity of the oracle's first (warm-up) step; north-star bar 1e-4 px for the fp32 path
         hip_out, hip_vals, hip_sets = hip_first_step(args.arch, settings, dev, args.dtype)
@@ -761,14 +821,14 @@ def main():
                                      'oracle/make_golden.py case mf_512x432_bs1, 8 torch threads)'})
 
     extra_sf, strict_leg = None, None
-    if rank == 0 and world == 1 and mf and not args.no_extra_legs and args.dtype == 'f32':
+    if args.full and rank == 0 and world == 1 and mf and not args.no_extra_legs and args.dtype == 'f32':
         # fresh child processes (their own GPU context), after everything of this run has been measured
         import subprocess
         torch.cuda.synchronize()
 
         def child(extra, env_extra=None):
             cmd = [sys.executable, os.path.abspath(__file__), '--steps', str(max(5, args.steps // 2)), '--warmup', '3',
-                   '--no-cpu-baseline', '--no-extra-legs', '--no-eager-leg'] + extra
+                   '--full', '--no-cpu-baseline', '--no-extra-legs', '--no-eager-leg'] + extra
             out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                                  env=dict(os.environ, **(env_extra or {})))
             try:
@@ -807,7 +867,7 @@ def main():
             'metric': ('DIS-MF train frames/sec bs=4 default-pattern' if mf else
                        f'DIS-SF train frames/sec bs={args.bs} default-pattern ({"bf16 activation storage" if args.dtype == "bf16" else "fp32"})'),
             'value': frames / dt, 'unit': 'frames/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'full': args.full,
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype,
             'dtype_note': ('fp32 tensors and results; the 3x3 16/32-channel convs multiply 22-bit two-term fp16 operands (config.conv_arithmetic); the >= 24-bit form of the same step is `strict_fp32_frames_per_s`' if (args.dtype == 'f32' and mf) else None),
             'data': 'synthetic',

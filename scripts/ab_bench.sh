@@ -4,8 +4,8 @@
 TAG=$1; A=$2; B=$3; R=${4:-2}; shift 4 2>/dev/null
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 run() { # name lib round
-  if [ "$2" = default ]; then env -u DIS_HIP_LIB python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs "${EXTRA[@]}" > $OUT/$1_$3.json 2> $OUT/$1_$3.err
-  else DIS_HIP_LIB=$2 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs "${EXTRA[@]}" > $OUT/$1_$3.json 2> $OUT/$1_$3.err; fi
+  if [ "$2" = default ]; then env -u DIS_HIP_LIB python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-extra-legs "${EXTRA[@]}" > $OUT/$1_$3.json 2> $OUT/$1_$3.err
+  else DIS_HIP_LIB=$2 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-extra-legs "${EXTRA[@]}" > $OUT/$1_$3.json 2> $OUT/$1_$3.err; fi
   python - $OUT/$1_$3.json $1 <<'PY'
 import json, sys
 try:

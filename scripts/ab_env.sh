@@ -2,7 +2,7 @@
 # usage: ab_env.sh <tag> "<envA>" "<envB>" rounds
 TAG=$1; A=$2; B=$3; R=${4:-2}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-run() { env $2 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extra-legs > $OUT/$1_$3.json 2> $OUT/$1_$3.err
+run() { env $2 python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-extra-legs > $OUT/$1_$3.json 2> $OUT/$1_$3.err
   python - $OUT/$1_$3.json "$1 [$2]" <<'PY'
 import json, sys
 try:

@@ -25,32 +25,21 @@ Only tests/ may import this module.
 """
 import ctypes
 import os
-import subprocess
 import numpy as np
 
+from oracle.dis_oracle import host_lib, vfma as fma   # noqa: F401 (the host helper library, shared with the oracle)
+
 f32 = np.float32
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
 
 
-def host_lib():
-    global _LIB
-    if _LIB is None:
-        path = os.path.join(_ROOT, 'oracle', '_build', 'libdis_host.so')
-        if not os.path.exists(path):
-            subprocess.check_call(['make', '-C', os.path.join(_ROOT, 'oracle')])
-        _LIB = ctypes.CDLL(path)
-        _LIB.heapsel_mismatches.restype = ctypes.c_long
-    return _LIB
-
-
-def fma(a, b, c):
-    a, b, c = np.broadcast_arrays(np.asarray(a, f32), np.asarray(b, f32), np.asarray(c, f32))
-    a, b, c = np.ascontiguousarray(a), np.ascontiguousarray(b), np.ascontiguousarray(c)
-    o = np.empty(a.shape, f32)
-    P = ctypes.c_void_p
-    host_lib().vfma(P(a.ctypes.data), P(b.ctypes.data), P(c.ctypes.data), P(o.ctypes.data), ctypes.c_long(a.size))
-    return o
+def mkl_rounds_as_fixture_host():
+    """Whether torch's MKL (its CPU BLAS and vector math) rounds as on the host the reference fixtures were recorded on: its
+    torch.sqrt and torch.exp reproduce tests/golden/mkl_probe.npz, written on a host whose MKL reproduces every reference
+    fixture bit for bit.  MKL picks its kernels by CPU: on other CPUs (or under MKL_ENABLE_INSTRUCTIONS=AVX2) these, its K = 3
+    sgemm and its convolutions round differently."""
+    import torch
+    G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'mkl_probe.npz'))
+    return all(np.array_equal(f(torch.from_numpy(G[k + '_x'])).numpy(), G[k + '_y']) for k, f in (('sqrt', torch.sqrt), ('exp', torch.exp)))
 
 
 def mul(a, b):

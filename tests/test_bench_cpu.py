@@ -92,3 +92,30 @@ def test_conv3x3_form_table_reads_the_recorded_int_arguments():
     assert lib.SIGS['dis_conv2d_dgrad_bf16x3_gnsums_res'].count('i') == 9
     assert lib.SIGS['dis_conv2d_fwd_bf16x3_oihw'].count('i') == 13
     assert lib.SIGS['dis_conv2d_fwd_bf16x3_gn'].count('i') == 12
+
+
+def test_dump_outputs_samples_large_arrays_at_fixed_indices(tmp_path):
+    """--dump-outputs: an array longer than DUMP_MAX_ELEMS (DIS-SF: 31.6 M parameters, 7.1 M disparities) is written at the same
+    sorted, distinct indices on every run; shorter ones (the loss terms, DIS-MF's parameters) are written whole."""
+    import types
+    n = 31595332
+    i = torch.arange((n + 3) // 4 * 4)
+    # the entry's index, exactly representable in fp32 as (i // 4096, i % 4096): parameters carry the low part, disparity the high
+    opt = types.SimpleNamespace(n=n, flat_p=(i % 4096).float())
+    disparity = (i[:n] // 4096).float().reshape(-1, 1, 1)
+    stepper = types.SimpleNamespace(loss_buf=torch.arange(32, dtype=torch.float32), nterms=7)
+    dirs = [tmp_path / 'a', tmp_path / 'b']
+    for d in dirs:
+        bench.dump_outputs(str(d), stepper, opt, disparity)
+    out = [{f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))} for d in dirs]
+    assert sorted(out[0]) == ['disparity', 'loss_terms', 'parameters']
+    for k in out[0]:
+        assert out[0][k].dtype == np.float32 and np.array_equal(out[0][k], out[1][k]), k
+    assert np.array_equal(out[0]['loss_terms'], np.arange(7, dtype=np.float32))
+    idx = out[0]['disparity'].astype(np.int64) * 4096 + out[0]['parameters'].astype(np.int64)
+    assert len(idx) == bench.DUMP_MAX_ELEMS and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < n
+    assert sum(os.path.getsize(str(dirs[0] / f)) for f in os.listdir(str(dirs[0]))) <= 64 << 20
+    small = types.SimpleNamespace(n=508993, flat_p=torch.arange(508996, dtype=torch.float32))
+    bench.dump_outputs(str(tmp_path / 'c'), stepper, small, torch.ones(4, 4, 1, 512, 432))
+    assert np.array_equal(np.load(str(tmp_path / 'c' / 'parameters.npy')), np.arange(508993, dtype=np.float32))
+    assert np.load(str(tmp_path / 'c' / 'disparity.npy')).shape == (4 * 4 * 512 * 432,)

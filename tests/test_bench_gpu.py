@@ -22,8 +22,35 @@ def _run(args, timeout=900):
     return json.loads(lines[0])
 
 
+def test_plain_line_times_the_steps_and_dumps_the_same_last_step_every_run(tmp_path):
+    """A plain run reports the timed steps only (every --full field null); --dump-outputs writes what the last timed step gives
+    its caller - loss terms (= the line's), disparity and updated parameters, DIS-MF whole - and, every step training from the
+    same seeded state, two runs write the same outputs: the tolerances of tests/test_determinism_gpu.py for one step (the
+    forward and the losses repeat bit for bit in practice, an Adam update moves a parameter by ~1e-4, run-to-run noise ~4e-8)."""
+    import numpy as np
+    outs = []
+    for r in ('a', 'b'):
+        d = _run(['--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / r)])
+        assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['full'] is False
+        assert abs(d['value'] - 4 * 4 * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+        for k in ('roofline', 'roofline_hbm_kernels', 'cpu_baseline', 'disp_l1_vs_ref', 'strict_fp32_frames_per_s', 'extra_dis_sf',
+                  'eager_launch_frames_per_s', 'kernel_ms_one_eager_step'):
+            assert d[k] is None, k
+        assert d['adam_steps_taken'] == 4
+        out = {f[:-4]: np.load(str(tmp_path / r / f)) for f in os.listdir(str(tmp_path / r))}
+        assert sorted(out) == ['disparity', 'loss_terms', 'parameters']
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+        assert np.array_equal(out['loss_terms'], np.asarray(d['loss_terms'], np.float32))
+        assert out['parameters'].shape == (508993,) and out['disparity'].shape == (4 * 4 * 512 * 432,)
+        outs.append(out)
+    a, b = outs
+    assert np.abs(a['disparity'] - b['disparity']).max() < 1e-5
+    np.testing.assert_allclose(a['loss_terms'], b['loss_terms'], rtol=1e-6, atol=0)
+    assert np.abs(a['parameters'] - b['parameters']).max() < 1e-6
+
+
 def test_single_gpu_line_roofline_covers_the_whole_kernel_family():
-    d = _run(['--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-extra-legs'])
+    d = _run(['--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-extra-legs'])
     assert d['n_gpus'] == 1 and d['config']['hip_graph'] is True and d['step_mode'] == 'graph'
     r = d['roofline']
     # the two kernel families of the 3x3 32 -> 32 layers: conv_f16x2_kernel (forward, GroupNorm-on-load forward, the input gradients that
@@ -48,7 +75,7 @@ def test_single_gpu_line_roofline_covers_the_whole_kernel_family():
 
 
 def test_two_ranks_gloo_bench_runs_and_replicas_agree():
-    d = _run(['--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--no-cpu-baseline'])
+    d = _run(['--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline'])
     assert d['n_gpus'] == 2 and d['ranks_seen'] == [0, 1]
     assert d['replicas_equal'] is True
     assert d['config']['global_batch'] == 8 and d['config']['parallelism'] == 'dp2'

@@ -44,6 +44,10 @@ def test_geometry_keys_and_topk_bit_exact(cfg):
         assert eq(B.resize_flow(flow[k].numpy(), h, w), flow_core[k].numpy()), k
     ex, em = B.mf_geometry(depth_core.numpy(), ray.numpy(), tb['R'].numpy(), tb['t'].numpy(),
                            {k: v.numpy() for k, v in flow_core.items()})
+    if B.mkl_rounds_as_fixture_host():   # O.matmul3 (mf_geometry's K = 3 products) is what torch itself computes there, at these shapes
+        xyz = depth_core.reshape(4, bs, -1, 1) * ray.view(1, 1, -1, 3) - tb['t'].view(4, bs, 1, 3)
+        for M in (tb['R'], tb['R'][1].transpose(1, 2)):
+            assert torch.equal(O.matmul3(xyz, M), torch.matmul(xyz, M))
     assert eq(ex, wxyz.numpy()) and eq(em, wmask.numpy())
     hq, wq = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
     wxyz_q = O.resize_ac(wxyz, (hq, wq))
@@ -84,6 +88,10 @@ def test_loss_masks_bit_exact(cfg):
                                             primary_depth1=pdepth[j].numpy() if mf else None)
             assert np.array_equal(m, mask.numpy())
             _, d1o = O.project(O.unproject(depth[i], ray, tb['R'][i], tb['t'][i]), K, tb['R'][j], tb['t'][j])
+            if B.mkl_rounds_as_fixture_host():   # O.unproject / O.project's K = 3 products are torch.bmm's there
+                xw = depth[i].reshape(bs, -1, 1) * ray.unsqueeze(0) - tb['t'][i].reshape(bs, 1, 3)
+                for M in (tb['R'][i], K.view(1, 3, 3).transpose(1, 2).expand(bs, -1, -1)):
+                    assert torch.equal(O.matmul3(xw, M), torch.bmm(xw, M))
             assert np.array_equal(d1.reshape(-1), d1o.numpy().reshape(-1))
 
 
