@@ -161,6 +161,21 @@ def test_bwd_fused_is_reproducible_and_handles_extreme_ranges():
     torch.cuda.synchronize()
     for o in outs[1:]:
         assert all(torch.equal(a_, b_) for a_, b_ in zip(o, outs[0]))
+    # gx against fp64, overall and per sample (sample 1 is the 1e-6 one), beside the three-term kernel: 4 x its error + 2e-7
+    from tests.conftest import conv_split
+    with conv_split('bf16x3'):
+        gx3 = torch.empty_like(x)
+        L.call('dis_conv2d_fwd_bf16x3_oihw', gy, wt, 1, c, c, wt.stride(0), None, gx3, None, n, h, w, c, c, 3, 1, 1, 0)
+    torch.cuda.synchronize()
+    gn = gy.permute(0, 3, 1, 2).double().cpu()
+    gx64 = torch.nn.grad.conv2d_input((n, c, h, w), wt.double().cpu(), gn, padding=1).permute(0, 2, 3, 1)
+    for s in [None] + list(range(n)):
+        sl = slice(None) if s is None else s
+        ref = gx64[sl]
+        e2 = float((outs[0][0][sl].double().cpu() - ref).abs().max() / ref.abs().max())
+        e3 = float((gx3[sl].double().cpu() - ref).abs().max() / ref.abs().max())
+        print('gx vs fp64, %s: fused %.2e, bf16x3 %.2e' % ('all' if s is None else 'sample %d' % s, e2, e3))
+        assert e2 < 4 * e3 + 2e-7, (s, e2, e3)
     gw64, gb64 = _fp64_wgrad(x, gy)
     assert bool(torch.isfinite(outs[0][1]).all())
     assert float((outs[0][1].double() - gw64).abs().max()) < 1e-6 * float(gw64.abs().max())
