@@ -2260,8 +2260,8 @@ static int launch_wgrad_bf16x3(WgArgs a, float* gw, float* gb, int cin_real, hip
  * DIS_ERR_UNSUPPORTED: no instance for this combination (the caller keeps the two launches). */
 extern "C" long dis_conv2d_bwd_fused_workspace(int c) {
   if (c != 32) return -1;
-  // the weight-gradient kernels' slabs + bias partials, then one spill slab per (workgroup, wave) for passes that end early (rare)
-  return wgrad_ws<32, 32, 3, 3, 1>() + (long)WG_WORKERS * 4 * 9 * 32 * 32;
+  // the weight-gradient kernels' slabs + bias partials (a pass that ends early flushes its dW accumulators into the slab)
+  return wgrad_ws<32, 32, 3, 3, 1>();
 }
 extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const float* coef, int in_act, float* gpre_out,
                                           const float* w_oihw, int w_o, int w_i, int w_row_stride, float* gx, int accumulate,
@@ -2314,7 +2314,6 @@ extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const 
   f.part = workspace;
   float* tmp = workspace + (long)WG_WORKERS * elems;
   f.bpart = grad_b ? tmp + (long)WG_RSPLIT * elems : nullptr;
-  f.spill = workspace + wgrad_ws<32, 32, 3, 3, 1>();
   hipStream_t s = (hipStream_t)stream;
   hipError_t le = dis_fb_launch(f, in_act, x_gn_stats != nullptr, xsrc, grid, s);
   if (le == hipErrorInvalidValue) return DIS_ERR_UNSUPPORTED;

@@ -101,8 +101,19 @@ def _mark_lazy_ok(out):
         out[0].grad_fn.lazy_uid = uid
 
 
+def _gn_coef(n, c, device):
+    """the per-(sample, channel) coefficients of a GroupNorm backward formed from channel sums (dis_gn_bwd_coef / _from_sums)"""
+    return torch.empty(n * (c + 2) + 4 * n * c + 2, dtype=torch.float32, device=device)
+
+
+def _gn_sums(n, c, device):
+    """-> (ab, slots): zeroed per-workgroup slots for the GroupNorm-backward channel sums an input-gradient epilogue leaves"""
+    slots = lib.fn('dis_conv2d_gnsums_slots')()
+    return _zeros_d(n * slots * 2 * c, device), slots
+
+
 def _gn_lazy_defer(g, q, stats, gamma, ab, slots, gg, gb, n, hw, c, eps, in_act, uid=0):
-    coef = torch.empty(n * (c + 2) + 4 * n * c + 2, dtype=torch.float32, device=g.device)
+    coef = _gn_coef(n, c, g.device)
     lib.call('dis_gn_bwd_coef', stats, gamma, ab, slots, coef, gg, gb, _zeros_d(1, g.device), n, hw, c, eps)
     tok = _new_token(g.device)
     _GN_LAZY[tok.data_ptr()] = (tok, g, q, coef, in_act)
@@ -365,6 +376,31 @@ class GradJoin(object):
         b, self.buf = self.buf, None
         return b.view(shape)
 
+    def target(self, like, new=torch.empty_like):
+        """-> (buffer the gradient wrt `like` is written into, accumulate): the stored buffer when the other consumer ran first"""
+        if self.buf is None:
+            return new(like), False
+        return self.take(like.shape), True
+
+    def result(self, g, accumulated):
+        """what autograd should see once g (from target()) is written"""
+        return g if accumulated else self.first(g)
+
+
+class _SoleConsumer(object):
+    """GradJoin's stand-in where the tensor has one consumer: a fresh buffer, the gradient goes to autograd"""
+
+    @staticmethod
+    def target(like, new=torch.empty_like):
+        return new(like), False
+
+    @staticmethod
+    def result(g, accumulated):
+        return g
+
+
+_SOLE = _SoleConsumer()
+
 
 class GradAccum(object):
     """Shared gradient buffer of a tensor with SEVERAL consumers whose backward kernels accumulate (+= / atomics) into
@@ -453,6 +489,19 @@ def _sink_opt(param):
     runs an AccumulateGrad node that an earlier, still referenced eager step created on the default stream - joining the
     legacy default stream into a capture crashes the HIP runtime."""
     return _sink(param) if param is not None else (None, None)
+
+
+def _into_sinks(weight, bias, grads, launch):
+    """launch(gw, gb) -> bool writes a weight / bias gradient: into grads = (gw, gb) when given, else into the sinks of weight / bias,
+    which go back when the launch did not run (False).  -> (ran, gw_ret, gb_ret)"""
+    if grads is not None:
+        return launch(*grads), None, None
+    got = (_sink(weight), _sink_opt(bias))
+    if launch(got[0][0], got[1][0]):
+        return True, got[0][1], got[1][1]
+    for p_, g_ in zip((weight, bias), got):
+        _unsink(p_, g_)
+    return False, None, None
 
 
 def _sink_block(params):
@@ -1134,43 +1183,109 @@ BWD_FUSED = _os.environ.get('DIS_BWD_FUSED', '1') != '0'
 _FUSED_WS = {}
 
 
-# DIS_WGRAD_ACT=0: the 4 -> 16 stems run dis_act_bwd + dis_conv2d_wgrad instead of dis_conv2d_wgrad_act (A/B only)
-WGRAD_ACT = _os_env.environ.get('DIS_WGRAD_ACT', '1') != '0'
-# DIS_GW_INPLACE=0: conv2d_multi's fused launches write their weight-gradient slice to a temporary that is copied into the full
-# gradient afterwards (the form before the slab reduce took a row pitch; A/B only)
-GW_INPLACE = _os_env.environ.get('DIS_GW_INPLACE', '1') != '0'
-
-
-def _gw_slice(gw, off, cs_i):
-    if GW_INPLACE:
-        return gw[:, off:off + cs_i]
-    return torch.empty((gw.shape[0], cs_i, gw.shape[2], gw.shape[3]), dtype=torch.float32, device=gw.device)
-
-
-def _bwd_fused_ok(cin, cout, k, stride, pad):
-    return BWD_FUSED and BF16X3 and cin == 32 and cout == 32 and k == 3 and stride == 1 and pad == 1
-
-
-def _bwd_fused(g, q, coef, in_act, gpre_out, weight, gx, accumulate, ab_x, ab_act, ab, x, xgn, gw, gb, n, h, w):
-    """one launch for both gradients of a 3x3 stride-1 pad-1 conv 32 -> 32; False: no instance (the caller runs its two launches).
-    xgn = (stats, gamma, beta, eps) when the conv's input is GroupNorm(x) applied on load, else None"""
-    c = x.shape[-1]
-    wsz = _FUSED_WS.get(c)
-    if wsz is None:
-        wsz = _FUSED_WS[c] = lib.fn('dis_conv2d_bwd_fused_workspace')(c)
-    if wsz < 0:
-        return False
-    ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
-    st, gam, bet, eps = xgn if xgn is not None else (None, None, None, 0.0)
-    # gw may be the (c, c, 3, 3) slice of a wider OIHW gradient (conv2d_multi): the slab reduce writes it in place
-    assert tuple(gw.stride()[1:]) == (9, 3, 1) and gw.stride(0) % 9 == 0
-    return lib.call_try('dis_conv2d_bwd_fused_f16x2', g, q, coef, in_act, gpre_out, weight, weight.shape[0], weight.shape[1],
-                        weight.stride(0), gx, 1 if accumulate else 0, ab_x, ab_act, ab, x, st, gam, bet, float(eps), gw, gb, ws, n, h, w, c,
-                        0 if gw.is_contiguous() else gw.stride(0))
+def _with_stats(ctx, y, stats):
+    """a conv forward's outputs (y, stats | None); the statistics have no gradient (and get no zero tensor for one)"""
+    if stats is not None:
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+    return y, stats
 
 
 def _bx_shape(cin, cout, k, stride):
     return BF16X3 and cin in (16, 32) and cout in (16, 32) and k == 3 and stride == 1
+
+
+def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=None, gy=None, act=ACT_NONE, y=None, xgn=None,
+                    sums=None, keep_gpre=False, after_dgrad=None):
+    """Both gradients of one stride-1 conv weight slice: a conv2d, a conv2d_gn_in, one source of conv2d_multi.  Which launches
+    serve which form is decided here and nowhere else.
+      operand: lz, a GroupNorm token (_gn_lazy_pop), whose elementwise pass the input-gradient launch forms on load; else gy, taken
+               times act'(y) on load when act != ACT_NONE (the bf16x3 shapes) and as the pre-activation gradient otherwise
+      x: the conv's input; xgn = (stats, gamma, beta, eps): the conv stages GroupNorm(x) (conv2d_gn_in)
+      gx: input-gradient target (None: not wanted), accumulate: add to what it holds; sums = (ab_x, ab_act): its launch also leaves
+          the GroupNorm-backward channel sums of ab_x - without xgn for the GroupNorm that produced x (_GN_PRE)
+      grads = (gw, gb): the weight / bias gradient targets (gw may be a slice of a wider gradient); None: the sinks of weight / bias
+      keep_gpre: the operand formed from a token is stored for the caller (conv2d_multi's other sources read it)
+      after_dgrad(ab, slots): runs once the input gradient is written, before the weight gradient (the GroupNorm backward of xgn)
+    -> (the weight gradient's operand, gw_ret, gb_ret, what after_dgrad returned)"""
+    cout, cin, k, _ = weight.shape
+    n, h, w, cin_pad = x.shape
+    split = lib.fn('dis_get_conv_split')() == 1
+    epi = gx is not None and sums is not None and split and act == ACT_NONE and cin == cout and _bx_shape(cin, cout, k, 1)
+    if lz is not None and not (gx is not None and split and act == ACT_NONE and cin_pad == cin and
+                               _gn_lazy_shape(cin, cout, k, 1, pad) and (xgn is None or epi)):
+        gy, lz = _gn_lazy_materialize(lz), None
+    # one launch for both gradients (csrc/conv_bwd_fused.hip, 32 -> 32): it forms a token's operand (and stores it only in the
+    # GroupNorm-on-load form) or takes gy (no epilogue then)
+    fused = (gx is not None and split and BWD_FUSED and BF16X3 and cin == cout == 32 and (k, pad) == (3, 1) and
+             ((not keep_gpre or xgn is not None) if lz is not None else (sums is None and xgn is None)))
+    if fused and cin not in _FUSED_WS:
+        _FUSED_WS[cin] = lib.fn('dis_conv2d_bwd_fused_workspace')(cin)
+    fused = fused and _FUSED_WS[cin] >= 0
+    ab, slots = _gn_sums(n, cin, x.device) if epi else (None, 0)
+    ab_x, ab_act = sums if epi else (None, None)
+    acc = 1 if accumulate else 0
+
+    def dgrad_done():
+        if ab is not None and xgn is None:
+            _GN_PRE[gx.data_ptr()] = (ab, slots)
+        return after_dgrad(ab, slots) if after_dgrad is not None else None
+
+    if lz is not None:
+        _, g, q, coef, in_act = lz
+        gpre = torch.empty_like(g) if keep_gpre else None
+    else:
+        g, q, coef, in_act, gpre = gy, (y if act != ACT_NONE else None), None, act, gy
+    if fused:
+        def launch(gw, gb):   # (gw may be the slice of a wider OIHW gradient, conv2d_multi: the slab reduce writes it in place)
+            assert tuple(gw.stride()[1:]) == (9, 3, 1) and gw.stride(0) % 9 == 0
+            st, gam, bet, eps = xgn if xgn is not None else (None, None, None, 0.0)
+            return lib.call_try('dis_conv2d_bwd_fused_f16x2', g, q, coef, in_act, gpre if lz is not None else None, weight, cout, cin,
+                                weight.stride(0), gx, acc, ab_x, ab_act, ab, x, st, gam, bet, float(eps), gw, gb,
+                                torch.empty(_FUSED_WS[cin], dtype=torch.float32, device=x.device), n, h, w, cin,
+                                0 if gw.is_contiguous() else gw.stride(0))
+        ok, gw_ret, gb_ret = _into_sinks(weight, bias, grads, launch)
+        if ok:
+            return gpre, gw_ret, gb_ret, dgrad_done()
+    after = None
+    if lz is not None:
+        gpre = torch.empty_like(g) if gpre is None else gpre
+        if not lib.call_try('dis_conv2d_dgrad_f16x2_gnb', g, q, coef, in_act, gpre, weight, cout, cin, weight.stride(0), gx, acc,
+                            ab_x, ab_act, ab, n, h, w, cin):
+            # (no instance in this build: the pass as a launch of its own, then the forms of a plain operand)
+            return _conv_bwd_slice(weight, x, gx, accumulate, grads, bias, pad, gy=_gn_lazy_materialize(lz), xgn=xgn, sums=sums,
+                                   keep_gpre=keep_gpre, after_dgrad=after_dgrad)
+        after = dgrad_done()
+    elif gx is not None:
+        kw = (n, gy.shape[1], gy.shape[2], cout, cin, k - 1 - pad)
+        if act != ACT_NONE:
+            lib.call('dis_conv2d_dgrad_bf16x3_act', gy, y, act, weight, cout, cin, weight.stride(0), gx, *kw, acc)
+        elif ab is not None and accumulate:
+            lib.call('dis_conv2d_dgrad_bf16x3_gnsums_res', gy, weight, cout, cin, weight.stride(0), gx, ab_act, ab_x, ab, *kw)
+        elif ab is not None:
+            lib.call('dis_conv2d_dgrad_bf16x3_gnsums', gy, weight, cout, cin, weight.stride(0), gx, ab_x, ab, *kw)
+        else:
+            _conv_fwd_any(gy, weight, cin, 1, None, gx, None, n, gy.shape[1], gy.shape[2], cout, cin, k, 1, k - 1 - pad,
+                          ACT_NONE | (CONV_ACCUM if accumulate else 0))
+        after = dgrad_done()
+
+    def wgrad(gw, gb):
+        gwc = gw if gw.is_contiguous() else torch.empty(gw.shape, dtype=torch.float32, device=gw.device)
+        wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin_pad, cout, k, 1)
+        if wsz < 0:
+            raise lib.DisHipError(f'conv2d wgrad: unsupported shape cin={cin_pad} cout={cout} k={k}')
+        ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
+        if xgn is not None:
+            lib.call('dis_conv2d_wgrad_bf16x3_gn', x, *xgn, gpre, gwc, gb, ws, n, h, w, cin, cin, cout, k, 1, pad)
+        elif act != ACT_NONE:
+            lib.call('dis_conv2d_wgrad_bf16x3_act', x, gy, y, act, gwc, gb, ws, n, h, w, cin_pad, cin, cout, k, 1, pad)
+        else:
+            _conv_wgrad_any(x, gpre, gwc, gb, ws, n, h, w, cin_pad, cin, cout, k, 1, pad)
+        if gwc is not gw:
+            gw.copy_(gwc)   # (a small strided move into the slice of the wider gradient)
+        return True
+    _, gw_ret, gb_ret = _into_sinks(weight, bias, grads, wgrad)
+    return gpre, gw_ret, gb_ret, after
 
 
 class _Conv2d(torch.autograd.Function):
@@ -1204,11 +1319,7 @@ class _Conv2d(torch.autograd.Function):
         ctx.cfg = (stride, pad, act, bias is not None, need_dgrad)
         ctx.bias_ref = bias  # only its address/shape are used (gradient sink lookup)
         ctx.join = join
-        if want_stats:
-            ctx.mark_non_differentiable(stats)
-            ctx.set_materialize_grads(False)  # no zero tensor for the statistics' (non-existent) gradient
-            return y, stats
-        return y, None
+        return _with_stats(ctx, y, stats)
 
     @staticmethod
     def backward(ctx, gy, _gstats):
@@ -1216,167 +1327,89 @@ class _Conv2d(torch.autograd.Function):
         stride, pad, act, has_bias, need_dgrad = ctx.cfg
         n, hin, win, cin_pad = x.shape
         cout, cin, k, _ = weight.shape
+        join = ctx.join or _SOLE
+        want_gx = need_dgrad and ctx.needs_input_grad[0]
         # a token of a GroupNorm behind this conv (ops._GN_LAZY): its backward's elementwise pass is applied by this conv's
         # input-gradient launch on load, which also writes the values for the weight-gradient launch
         lz = _gn_lazy_pop(gy, ctx)
-        if (lz is not None and act == ACT_NONE and _gn_lazy_k4s2(cin_pad, cin, cout, k, stride, pad) and
-                lib.fn('dis_get_conv_split')() == 1 and x[0].numel() * 4 < 0x7fff0000):   # (the kernel's per-sample 31-bit offsets)
-            # the 4 x 4 stride-2 down convolution: the WEIGHT-gradient launch applies the pass while it stages gy (no halo there)
-            # and stores the values for the four parity launches of the input gradient
-            _, lg, lq, lcoef, lin_act = lz
-            gpre = torch.empty_like(lg)
-            gw, gw_ret = _sink(weight)
-            gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
-            ws = torch.empty(lib.fn('dis_conv2d_wgrad_workspace')(cin_pad, cout, k, stride), dtype=torch.float32, device=x.device)
-            if lib.call_try('dis_conv2d_wgrad_k4s2_f16x2_gnb', x, lg, lq, lcoef, lin_act, gpre, gw, gb, ws, n, hin, win):
-                gx = None
-                if need_dgrad and ctx.needs_input_grad[0]:
-                    join = ctx.join
-                    second = join is not None and join.buf is not None
-                    gx = join.take(x.shape) if second else torch.empty_like(x)
-                    _dgrad_k4s2(gpre, weight, gx, n, hin, win, cin, cout, second)
-                    if join is not None and not second:
-                        gx = join.first(gx)
-                _sinks_written()
-                return gx, gw_ret, gb_ret, None, None, None, None, None, None, None, None, None
-            # (no instance for this configuration in this build - e.g. an input activation the kernel has no form for: the sinks go
-            #  back, the pass runs as a launch of its own, the general path below does the rest)
-            _unsink(weight, (gw, gw_ret))
-            if has_bias:
-                _unsink(ctx.bias_ref, (gb, gb_ret))
-            gy, lz = _gn_lazy_materialize(lz), None
-        if lz is not None and not (act == ACT_NONE and need_dgrad and ctx.needs_input_grad[0] and cin_pad == cin and
-                                   _gn_lazy_shape(cin, cout, k, stride, pad) and lib.fn('dis_get_conv_split')() == 1):
-            gy, lz = _gn_lazy_materialize(lz), None
-        if lz is not None:
-            _, lg, lq, lcoef, lin_act = lz
-            join = ctx.join
-            second = join is not None and join.buf is not None
-            gx = join.take(x.shape) if second else torch.empty_like(x)
-            gnres = ctx.gnres
-            gpre = torch.empty_like(lg)
-            ab = ab_x = ab_act = None
-            if (gnres is not None and second and (GN_SUMS & 2) and tuple(gnres[0].shape) == tuple(x.shape)):
-                slots = lib.fn('dis_conv2d_gnsums_slots')()   # (the ResNetBlock-chain / two-consumer epilogue, see below)
-                ab = _zeros_d(n * slots * 2 * cin, x.device)
-                ab_x, ab_act = gnres[0], (x if len(gnres) == 1 else None)
-            if _bwd_fused_ok(cin, cout, k, stride, pad):
-                # one launch: the operand formed on load feeds the input gradient AND the weight gradient (gpre is never written)
-                gw, gw_ret = _sink(weight)
-                gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
-                if _bwd_fused(lg, lq, lcoef, lin_act, None, weight, gx, second, ab_x, ab_act, ab, x, None, gw, gb, n, hin, win):
-                    if ab is not None:
-                        _GN_PRE[gx.data_ptr()] = (ab, slots)
-                    if join is not None and not second:
-                        gx = join.first(gx)
-                    _sinks_written()
-                    return gx, gw_ret, gb_ret, None, None, None, None, None, None, None, None, None
-                _unsink(weight, (gw, gw_ret))
-                if has_bias:
-                    _unsink(ctx.bias_ref, (gb, gb_ret))
-            if lib.call_try('dis_conv2d_dgrad_f16x2_gnb', lg, lq, lcoef, lin_act, gpre, weight, cout, cin, weight.stride(0), gx,
-                            1 if second else 0, ab_x, ab_act, ab, n, hin, win, cin):
-                if ab is not None:
-                    _GN_PRE[gx.data_ptr()] = (ab, slots)
-                if join is not None and not second:
-                    gx = join.first(gx)
-                gw, gw_ret = _sink(weight)
-                gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
+        gw_ret = gb_ret = None
+        wdone = False
+        if lz is not None and (stride != 1 or act != ACT_NONE):
+            if (act == ACT_NONE and _gn_lazy_k4s2(cin_pad, cin, cout, k, stride, pad) and lib.fn('dis_get_conv_split')() == 1 and
+                    x[0].numel() * 4 < 0x7fff0000):   # (the kernel's per-sample 31-bit offsets)
+                # the 4 x 4 stride-2 down convolution: the WEIGHT-gradient launch applies the pass while it stages gy (no halo there)
+                # and stores the values for the four parity launches of the input gradient below
+                _, lg, lq, lcoef, lin_act = lz
+                gpre = torch.empty_like(lg)
                 ws = torch.empty(lib.fn('dis_conv2d_wgrad_workspace')(cin_pad, cout, k, stride), dtype=torch.float32, device=x.device)
-                _conv_wgrad_any(x, gpre, gw, gb, ws, n, hin, win, cin_pad, cin, cout, k, stride, pad)
-                _sinks_written()
-                return gx, gw_ret, gb_ret, None, None, None, None, None, None, None, None, None
-            # (no instance for this combination in this build: the separate pass, then the general path below)
-            if second:
-                join.buf = gx   # (hand the joined buffer back: the general path takes it again)
-            gy = _gn_lazy_materialize(lz)
-        gy = _c(gy)
+                ok, gw_ret, gb_ret = _into_sinks(weight, ctx.bias_ref, None, lambda gw, gb: lib.call_try(
+                    'dis_conv2d_wgrad_k4s2_f16x2_gnb', x, lg, lq, lcoef, lin_act, gpre, gw, gb, ws, n, hin, win))
+                if ok:
+                    gy, lz, wdone = gpre, None, True
+            # (no instance for this configuration in this build - e.g. an input activation the kernel has no form for: the pass
+            #  runs as a launch of its own, the general path below does the rest)
+            if lz is not None:
+                gy, lz = _gn_lazy_materialize(lz), None
+        if lz is None:
+            gy = _c(gy)
+        gpre = gy
         # bf16x3 shapes: the activation gradient is applied while gy is staged (dgrad and wgrad kernels), no separate pass
         fuse_act = act != ACT_NONE and _bx_shape(cin_pad, cout, k, stride)
         # the 4 -> 16 stems (conv1, amb_conv): no input gradient is asked for, so gy act'(y) would be formed for the weight-gradient
         # launch alone - that launch forms it on load (dis_conv2d_wgrad_act), the pass (read gy, y; write gpre) does not exist
-        wgrad_act = (WGRAD_ACT and act != ACT_NONE and not fuse_act and not (need_dgrad and ctx.needs_input_grad[0]) and
-                     cin_pad == 4 and cout == 16 and (k, stride) in ((3, 1), (4, 2)))
+        wgrad_act = (act != ACT_NONE and not fuse_act and not want_gx and cin_pad == 4 and cout == 16 and
+                     (k, stride) in ((3, 1), (4, 2)))
         if act != ACT_NONE and not fuse_act and not wgrad_act:
             gpre = torch.empty_like(gy)
             lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
-        else:
-            gpre = gy
-        gx = None
-        if (need_dgrad and ctx.needs_input_grad[0] and cin_pad == cin and _bwd_fused_ok(cin, cout, k, stride, pad) and
-                (fuse_act or gpre is gy) and lib.fn('dis_get_conv_split')() == 1 and
-                not (ctx.gnres is not None and ctx.join is not None and ctx.join.buf is not None and (GN_SUMS & 2) and
-                     tuple(ctx.gnres[0].shape) == tuple(x.shape))):
-            # no GroupNorm-backward operand, no channel-sum epilogue: gy (or gy act'(y)) feeds both gradients in one launch
-            join = ctx.join
-            second = join is not None and join.buf is not None
-            gx = join.take(x.shape) if second else torch.empty_like(x)
-            gw, gw_ret = _sink(weight)
-            gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
-            if _bwd_fused(gy, y if fuse_act else None, None, act if fuse_act else ACT_NONE, None, weight, gx, second, None, None, None, x,
-                          None, gw, gb, n, hin, win):
-                if join is not None and not second:
-                    gx = join.first(gx)
-                _sinks_written()
-                return gx, gw_ret, gb_ret, None, None, None, None, None, None, None, None, None
-            _unsink(weight, (gw, gw_ret))
-            if has_bias:
-                _unsink(ctx.bias_ref, (gb, gb_ret))
-            if second:
-                join.buf = gx
-            gx = None
-        if need_dgrad and ctx.needs_input_grad[0]:
+        if want_gx:
             assert cin_pad == cin
-            join = ctx.join
-            second = join is not None and join.buf is not None
-            gx = join.take(x.shape) if second else torch.empty_like(x)
-            gnres = ctx.gnres
-            if (fuse_act and gnres is not None and join is None and act == ACT_SELU and (GN_SUMS & 1) and (cout, cin) == (16, 32) and
-                    tuple(gnres[0].shape) == tuple(x.shape) and lib.fn('dis_get_conv_split')() == 1):
-                # (final_conv: x = SELU(GroupNorm(.) + res) of ref_res3 and this conv is its only consumer - as below)
-                slots = lib.fn('dis_conv2d_gnsums_slots')()
-                ab = _zeros_d(n * slots * 2 * cin, x.device)
-                lib.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gy, y, weight, cout, cin, weight.stride(0), gx, x, gnres[0], ab,
-                         n, gy.shape[1], gy.shape[2], cout, cin, k - 1 - pad)
-                _GN_PRE[gx.data_ptr()] = (ab, slots)
-            elif fuse_act:
-                lib.call('dis_conv2d_dgrad_bf16x3_act', gy, y, act, weight, cout, cin, weight.stride(0), gx, n, gy.shape[1],
-                         gy.shape[2], cout, cin, k - 1 - pad, 1 if second else 0)
-            elif (gnres is not None and second and (GN_SUMS & 2) and _bx_shape(cin_pad, cout, k, stride) and cin == cout and
-                  tuple(gnres[0].shape) == tuple(x.shape) and lib.fn('dis_get_conv_split')() == 1 and gpre is gy):
-                # x is out = SELU(GroupNorm(x2) + res) of the previous ResNetBlock, and gx - which arrives holding this block's
-                # residual-branch gradient - becomes the complete gradient wrt out here.  The epilogue turns it into the gradient
-                # wrt the pre-activation value (times SELU'(x)) and leaves the GroupNorm-backward sums: that GroupNorm's backward
-                # then needs neither its reduce pass nor a residual-gradient write (_GroupNorm.backward looks the buffer up)
-                slots = lib.fn('dis_conv2d_gnsums_slots')()
-                ab = _zeros_d(n * slots * 2 * cin, x.device)
-                # (gnres = (x2,): x = SELU(GroupNorm(x2) + res); gnres = (x2, None): x = GroupNorm(x2) with two consumers, no SELU)
-                lib.call('dis_conv2d_dgrad_bf16x3_gnsums_res', gpre, weight, cout, cin, weight.stride(0), gx,
-                         x if len(gnres) == 1 else None, gnres[0], ab, n, gpre.shape[1], gpre.shape[2], cout, cin, k - 1 - pad)
-                _GN_PRE[gx.data_ptr()] = (ab, slots)
-            elif stride == 1:
-                _conv_fwd_any(gpre, weight, cin, 1, None, gx, None, n, gpre.shape[1], gpre.shape[2], cout, cin, k, 1,
-                              k - 1 - pad, ACT_NONE | (CONV_ACCUM if second else 0))
-            else:
+        gx = None
+        if stride != 1 or wgrad_act:
+            # the 4 x 4 stride-2 convolutions and the 4 -> 16 stems
+            if want_gx:
+                gx, second = join.target(x)
                 _dgrad_k4s2(gpre, weight, gx, n, hin, win, cin, cout, second)
-            if join is not None and not second:
-                gx = join.first(gx)
-        gw, gw_ret = _sink(weight)
-        gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
-        wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin_pad, cout, k, stride)
-        if wsz < 0:
-            raise lib.DisHipError(f'conv2d wgrad: unsupported shape cin={cin_pad} cout={cout} k={k} s={stride}')
-        ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
-        if fuse_act:
-            lib.call('dis_conv2d_wgrad_bf16x3_act', x, gy, y, act, gw, gb, ws, n, hin, win, cin_pad, cin, cout, k, stride,
-                     pad)
-        elif wgrad_act:
-            if not lib.call_try('dis_conv2d_wgrad_act', x, gy, y, act, gw, gb, ws, n, hin, win, cin_pad, cin, cout, k, stride, pad):
-                gpre = torch.empty_like(gy)   # (no instance in this build: the pass as a launch of its own)
-                lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
-                _conv_wgrad_any(x, gpre, gw, gb, ws, n, hin, win, cin_pad, cin, cout, k, stride, pad)
-        else:
-            _conv_wgrad_any(x, gpre, gw, gb, ws, n, hin, win, cin_pad, cin, cout, k, stride, pad)
+                gx = join.result(gx, second)
+            if not wdone:
+                gw, gw_ret = _sink(weight)
+                gb, gb_ret = _sink_opt(ctx.bias_ref)
+                wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin_pad, cout, k, stride)
+                if wsz < 0:
+                    raise lib.DisHipError(f'conv2d wgrad: unsupported shape cin={cin_pad} cout={cout} k={k} s={stride}')
+                ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
+                if wgrad_act and not lib.call_try('dis_conv2d_wgrad_act', x, gy, y, act, gw, gb, ws, n, hin, win, cin_pad, cin, cout,
+                                                  k, stride, pad):
+                    gpre = torch.empty_like(gy)   # (no instance in this build: the pass as a launch of its own)
+                    lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
+                    wgrad_act = False
+                if not wgrad_act:
+                    _conv_wgrad_any(x, gpre, gw, gb, ws, n, hin, win, cin_pad, cin, cout, k, stride, pad)
+            _sinks_written()
+            return gx, gw_ret, gb_ret, None, None, None, None, None, None, None, None, None
+        gnres = ctx.gnres
+        if (want_gx and fuse_act and gnres is not None and ctx.join is None and act == ACT_SELU and (GN_SUMS & 1) and
+                (cout, cin) == (16, 32) and tuple(gnres[0].shape) == tuple(x.shape) and lib.fn('dis_get_conv_split')() == 1):
+            # final_conv: x = SELU(GroupNorm(.) + res) of ref_res3 and this conv is its only consumer - its input-gradient launch
+            # leaves that GroupNorm's backward sums (as the residual form below)
+            gx = torch.empty_like(x)
+            ab, slots = _gn_sums(n, cin, x.device)
+            lib.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gy, y, weight, cout, cin, weight.stride(0), gx, x, gnres[0], ab,
+                     n, gy.shape[1], gy.shape[2], cout, cin, k - 1 - pad)
+            _GN_PRE[gx.data_ptr()] = (ab, slots)
+            want_gx = False
+        tgt, second = join.target(x) if want_gx else (None, False)
+        # x is out = SELU(GroupNorm(x2) + res) of the previous ResNetBlock (gnres = (x2,)), or GroupNorm(x2) with two consumers
+        # (gnres = (x2, None)), and gx - which arrives holding the other consumer's gradient - becomes the complete gradient wrt out
+        # here: the epilogue turns it into the gradient wrt the pre-activation value (times SELU'(x)) and leaves the
+        # GroupNorm-backward sums, so that GroupNorm's backward needs neither its reduce pass nor a residual-gradient write
+        sums = None
+        if second and gnres is not None and (GN_SUMS & 2) and tuple(gnres[0].shape) == tuple(x.shape):
+            sums = (gnres[0], x if len(gnres) == 1 else None)
+        _, gw_ret, gb_ret, _ = _conv_bwd_slice(weight, x, tgt, second, bias=ctx.bias_ref, pad=pad, lz=lz, gy=gy if fuse_act else gpre,
+                                               act=act if fuse_act else ACT_NONE, y=y, sums=sums)
+        if tgt is not None:
+            gx = join.result(tgt, second)
         _sinks_written()
         return gx, gw_ret, gb_ret, None, None, None, None, None, None, None, None, None
 
@@ -1414,6 +1447,40 @@ def gn_fusable(cin, cout, k, stride):
     return GN_FUSE and BF16X3 and cin == cout and cin in (16, 32) and k == 3 and stride == 1
 
 
+def _gn_bwd_from_sums(g, x, stats, gamma, ab, slots, gg, gb, eps, in_act, uid):
+    """GroupNorm(1 group) backward from the channel sums an earlier launch left (ab): a token when the producer of x redeems one
+    (uid, _GN_LAZY), else one elementwise pass.  -> gradient wrt x"""
+    n, c = x.shape[0], x.shape[-1]
+    hw = x.numel() // (n * c)
+    if uid and GN_LAZY:
+        return _gn_lazy_defer(g, x, stats, gamma, ab, slots, gg, gb, n, hw, c, eps, in_act, uid=uid)
+    gx = torch.empty_like(x)
+    lib.call('dis_gn_bwd_from_sums', g, x, stats, gamma, ab, slots, gx, gg, gb, _gn_coef(n, c, x.device), n, hw, c, eps, in_act)
+    return gx
+
+
+def _gn_apply_bwd(g, y, x, stats, gamma, gres, gg, gb, act, eps, in_act):
+    """GroupNorm(1 group) backward as a reduce and an apply launch over g (and y, x).  -> gradient wrt x"""
+    n, c = x.shape[0], x.shape[-1]
+    gx = torch.empty_like(x)
+    wtot = lib.fn('dis_gn_bwd_workspace')(n, c)
+    ws = torch.empty(wtot, dtype=torch.float64, device=x.device)
+    nred2 = wtot // (2 + 2 * c) * 2  # (n * blocks-per-sample-max) pairs of per-block sums, then the parameter partials
+    lib.call('dis_gn_apply_bwd', g, y, x, stats, gamma, gx, gres, gg, gb, ws[:nred2], ws[nred2:], n, x.numel() // (n * c), c, act,
+             eps, in_act)
+    return gx
+
+
+def _gn_bwd_after_dgrad(g, x, stats, gamma, beta, eps, in_act, ab, slots, uid):
+    """The backward of a GroupNorm that a conv applied on load (conv2d_gn_in), once that conv's input gradient g exists: from the
+    channel sums its launch left (ab), else the reduce and apply launches.  -> (gradient wrt x, gamma's and beta's for autograd)"""
+    gg, gg_ret = _sink(gamma)
+    gb, gb_ret = _sink(beta)
+    if ab is not None:
+        return _gn_bwd_from_sums(g, x, stats, gamma, ab, slots, gg, gb, eps, in_act, uid), gg_ret, gb_ret
+    return _gn_apply_bwd(g, None, x, stats, gamma, None, gg, gb, ACT_NONE, eps, in_act), gg_ret, gb_ret
+
+
 class _Conv2dGnIn(torch.autograd.Function):
     """y = act(conv3x3(GroupNorm(x)) + bias) where the GroupNorm (1 group; its statistics `gn_stats` come from the epilogue of
     the conv that produced x) is applied by the conv kernels while they stage x: the normalised tensor is never written or
@@ -1440,88 +1507,30 @@ class _Conv2dGnIn(torch.autograd.Function):
         ctx.save_for_backward(x, gn_stats, gamma, weight, y if act != ACT_NONE else None)
         ctx.cfg = (pad, act, bias is not None, float(eps), in_act)
         ctx.bias_ref, ctx.beta_ref = bias, beta
-        if want_stats:
-            ctx.mark_non_differentiable(stats)
-            ctx.set_materialize_grads(False)
-            return y, stats
-        return y, None
+        return _with_stats(ctx, y, stats)
 
     @staticmethod
     def backward(ctx, gy, _gstats):
         x, gn_stats, gamma, weight, y = ctx.saved_tensors
         pad, act, has_bias, eps, in_act = ctx.cfg
-        n, h, w, cin = x.shape
-        cout, _, k, _ = weight.shape
-        sums = (GN_SUMS & 4) and lib.fn('dis_get_conv_split')() == 1
-        # (this conv's own output gradient may be a token of the GroupNorm behind it: redeemed by the input-gradient launch below)
+        # (this conv's own output gradient may be a token of the GroupNorm behind it: redeemed by the input-gradient launch)
         lz = _gn_lazy_pop(gy, ctx)
-        if lz is not None and not (sums and act == ACT_NONE and _gn_lazy_shape(cin, cout, k, 1, pad)):
+        if lz is not None and act != ACT_NONE:
             gy, lz = _gn_lazy_materialize(lz), None
-        gnorm = torch.empty_like(x)
-        slots = lib.fn('dis_conv2d_gnsums_slots')() if sums else 0
-        ab = _zeros_d(n * slots * 2 * cin, x.device) if sums else None
-        gpre = None
-        fused_done = False
-        if lz is not None:
-            _, lg, lq, lcoef, lin_act = lz
-            if _bwd_fused_ok(cin, cout, k, 1, pad):
-                # one launch: input gradient (+ the channel sums for this node's own GroupNorm) and the weight gradient with the
-                # GroupNorm of x applied on load; x is fetched once for both
-                gw, gw_ret = _sink(weight)
-                gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
-                if _bwd_fused(lg, lq, lcoef, lin_act, None, weight, gnorm, False, x, None, ab, x, (gn_stats, gamma, ctx.beta_ref, eps), gw, gb,
-                              n, h, w):
-                    fused_done, gpre = True, lg   # (gpre: only its shape is used below)
-                else:
-                    _unsink(weight, (gw, gw_ret))
-                    if has_bias:
-                        _unsink(ctx.bias_ref, (gb, gb_ret))
-            if not fused_done:
-                gpre = torch.empty_like(lg)
-                if not lib.call_try('dis_conv2d_dgrad_f16x2_gnb', lg, lq, lcoef, lin_act, gpre, weight, cout, cin, weight.stride(0),
-                                    gnorm, 0, x, None, ab, n, h, w, cin):
-                    gy, gpre = _gn_lazy_materialize(lz), None
-        dgrad_done = gpre is not None
-        if not dgrad_done:
-            gy = _c(gy)
+        gpre = gy
+        if lz is None:
+            gy = gpre = _c(gy)
             if act != ACT_NONE:   # (not the case in the networks here: the consumers are followed by a GroupNorm themselves)
                 gpre = torch.empty_like(gy)
                 lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
-            else:
-                gpre = gy
-        # gradient wrt the normalised tensor, then through the GroupNorm to the producer's (pre-activation) output
-        gg, gg_ret = _sink(gamma)
-        gbt, gbt_ret = _sink(ctx.beta_ref)
-        hw = h * w
-        if sums:
-            # the input-gradient launch leaves the per-(sample, channel) sums of g and g * x in its epilogue: the GroupNorm
-            # backward is then ONE elementwise pass (no reduce pass over g and x) - applied by the producer's input-gradient
-            # launch on load when the producer redeems tokens (x_lazy), else a launch of its own
-            if not dgrad_done:
-                lib.call('dis_conv2d_dgrad_bf16x3_gnsums', gpre, weight, cout, cin, weight.stride(0), gnorm, x, ab, n, gpre.shape[1],
-                         gpre.shape[2], cout, cin, k - 1 - pad)
-            if ctx.x_lazy and GN_LAZY:
-                gx = _gn_lazy_defer(gnorm, x, gn_stats, gamma, ab, slots, gg, gbt, n, hw, cin, eps, in_act, uid=ctx.x_lazy)
-            else:
-                gx = torch.empty_like(x)
-                coef = torch.empty(n * (cin + 2) + 4 * n * cin + 2, dtype=torch.float32, device=x.device)
-                lib.call('dis_gn_bwd_from_sums', gnorm, x, gn_stats, gamma, ab, slots, gx, gg, gbt, coef, n, hw, cin, eps, in_act)
-        else:
-            gx = torch.empty_like(x)
-            _conv_fwd_any(gpre, weight, cin, 1, None, gnorm, None, n, gpre.shape[1], gpre.shape[2], cout, cin, k, 1, k - 1 - pad,
-                          ACT_NONE)
-            wtot = lib.fn('dis_gn_bwd_workspace')(n, cin)
-            ws = torch.empty(wtot, dtype=torch.float64, device=x.device)
-            nred2 = wtot // (2 + 2 * cin) * 2
-            lib.call('dis_gn_apply_bwd', gnorm, None, x, gn_stats, gamma, gx, None, gg, gbt, ws[:nred2], ws[nred2:], n, hw, cin,
-                     ACT_NONE, eps, in_act)
-        if not fused_done:
-            gw, gw_ret = _sink(weight)
-            gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
-            wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin, cout, k, 1)
-            wws = torch.empty(wsz, dtype=torch.float32, device=x.device)
-            lib.call('dis_conv2d_wgrad_bf16x3_gn', x, gn_stats, gamma, ctx.beta_ref, eps, gpre, gw, gb, wws, n, h, w, cin, cin, cout,
-                     k, 1, pad)
+        # gradient wrt the normalised tensor (the input-gradient launch leaves the per-(sample, channel) sums of g and g * x in
+        # its epilogue), then through the GroupNorm to the producer's (pre-activation) output
+        gnorm = torch.empty_like(x)
+        _, gw_ret, gb_ret, (gx, gg_ret, gbt_ret) = _conv_bwd_slice(
+            weight, x, gnorm, False, bias=ctx.bias_ref, pad=pad, lz=lz, gy=gpre, xgn=(gn_stats, gamma, ctx.beta_ref, eps),
+            sums=(x, None) if GN_SUMS & 4 else None,
+            after_dgrad=lambda ab, slots: _gn_bwd_after_dgrad(gnorm, x, gn_stats, gamma, ctx.beta_ref, eps, in_act, ab, slots,
+                                                              ctx.x_lazy))
         _sinks_written()
         return gx, None, gg_ret, gbt_ret, gw_ret, gb_ret, None, None, None, None, None, None, None
 
@@ -1582,11 +1591,7 @@ class _Conv2dMulti(torch.autograd.Function):
         ctx.save_for_backward(weight, y if act != ACT_NONE else None, gn_stats, gn_gamma, *xs)
         ctx.cfg = (pad, act, bias is not None, cs, gn_meta)
         ctx.bias_ref, ctx.beta_ref = bias, gn_beta
-        if want_stats:
-            ctx.mark_non_differentiable(stats)
-            ctx.set_materialize_grads(False)  # no zero tensor for the statistics' (non-existent) gradient
-            return y, stats
-        return y, None
+        return _with_stats(ctx, y, stats)
 
     @staticmethod
     def backward(ctx, gy, _gstats):
@@ -1600,131 +1605,49 @@ class _Conv2dMulti(torch.autograd.Function):
         # this conv's output gradient may be a token of the GroupNorm behind it (conv_fuse): the FIRST source's input-gradient launch
         # applies the elementwise pass on load and stores the result for every other launch of this node
         lz = _gn_lazy_pop(gy, ctx)
-        if lz is not None and not (act == ACT_NONE and ctx.lazy_ok and ctx.needs_input_grad[10] and
-                                   (gn_meta is None or (GN_SUMS & 8)) and lib.fn('dis_get_conv_split')() == 1):
+        if lz is not None and act != ACT_NONE:
             gy, lz = _gn_lazy_materialize(lz), None
+        gpre = gy
         if lz is None:
-            gy = _c(gy)
-        if lz is not None:
-            gpre = None   # (set by the first source's launch below)
-        elif act != ACT_NONE and not fuse_act:
-            gpre = torch.empty_like(gy)
-            lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
-        else:
-            gpre = gy
+            gy = gpre = _c(gy)
+            if act != ACT_NONE and not fuse_act:
+                gpre = torch.empty_like(gy)
+                lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
         gw, gw_ret = _sink(weight)
-        gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
+        gb, gb_ret = _sink_opt(ctx.bias_ref)
         gg_ret = gbt_ret = None
         gxs = []
         off = 0
-        need_w = [None]   # the weight gradient of the current slice when a fused launch has produced it
         for i, x in enumerate(xs):
             wi = weight[:, off:off + cs[i]]  # a view: no copy
-            gn0 = i == 0 and gn_meta is not None
-            gx = None
-            if ctx.needs_input_grad[10 + i]:
-                gx = torch.empty_like(x)
-                if gn0:
-                    # gradient wrt the normalised tensor, then through the GroupNorm (as _Conv2dGnIn.backward)
-                    eps, in_act = gn_meta
-                    gnorm = torch.empty_like(x)
-                    gg, gg_ret = _sink(gn_gamma)
-                    gbt, gbt_ret = _sink(ctx.beta_ref)
-                    if (GN_SUMS & 8) and lib.fn('dis_get_conv_split')() == 1:
-                        slots = lib.fn('dis_conv2d_gnsums_slots')()
-                        ab = _zeros_d(n * slots * 2 * cs[0], x.device)
-                        if lz is not None:
-                            _, lg, lq, lcoef, lin_act = lz
-                            gpre = torch.empty_like(lg)
-                            if _bwd_fused_ok(cs[0], cout, k, 1, pad) and need_w[0] is None:
-                                # one launch: operand formed on load (stored for the other sources' launches), input gradient +
-                                # channel sums, and this slice's weight / bias gradient with GroupNorm(x) on load
-                                gw0 = _gw_slice(gw, off, cs[0])   # (the slab reduce writes the slice of the full gradient in place)
-                                if _bwd_fused(lg, lq, lcoef, lin_act, gpre, wi, gnorm, False, x, None, ab, x,
-                                              (gn_stats, gn_gamma, ctx.beta_ref, float(gn_meta[0])), gw0, gb if has_bias else None, n, h, w):
-                                    need_w[0] = gw0
-                            if need_w[0] is not None:
-                                pass
-                            elif not lib.call_try('dis_conv2d_dgrad_f16x2_gnb', lg, lq, lcoef, lin_act, gpre, wi, cout, cs[0], wi.stride(0),
-                                                  gnorm, 0, x, None, ab, n, h, w, cs[0]):
-                                gpre = _gn_lazy_materialize(lz)   # (no instance in this build: the pass as a launch of its own)
-                                lib.call('dis_conv2d_dgrad_bf16x3_gnsums', gpre, wi, cout, cs[0], wi.stride(0), gnorm, x, ab, n,
-                                         gpre.shape[1], gpre.shape[2], cout, cs[0], k - 1 - pad)
-                            lz = None
-                        else:
-                            lib.call('dis_conv2d_dgrad_bf16x3_gnsums', gpre, wi, cout, cs[0], wi.stride(0), gnorm, x, ab, n,
-                                     gpre.shape[1], gpre.shape[2], cout, cs[0], k - 1 - pad)
-                        if ctx.x0_lazy and GN_LAZY:   # (the producer of xs[0] applies the elementwise pass on load: _GN_LAZY)
-                            gx = _gn_lazy_defer(gnorm, x, gn_stats, gn_gamma, ab, slots, gg, gbt, n, h * w, cs[0], float(eps), in_act, uid=ctx.x0_lazy)
-                        else:
-                            coef = torch.empty(n * (cs[0] + 2) + 4 * n * cs[0] + 2, dtype=torch.float32, device=x.device)
-                            lib.call('dis_gn_bwd_from_sums', gnorm, x, gn_stats, gn_gamma, ab, slots, gx, gg, gbt, coef, n, h * w,
-                                     cs[0], float(eps), in_act)
-                    else:
-                        _conv_fwd_any(gpre, wi, cs[0], 1, None, gnorm, None, n, gpre.shape[1], gpre.shape[2], cout, cs[0], k, 1,
-                                      k - 1 - pad, ACT_NONE)
-                        wtot = lib.fn('dis_gn_bwd_workspace')(n, cs[0])
-                        wsd = torch.empty(wtot, dtype=torch.float64, device=x.device)
-                        nred2 = wtot // (2 + 2 * cs[0]) * 2
-                        lib.call('dis_gn_apply_bwd', gnorm, None, x, gn_stats, gn_gamma, gx, None, gg, gbt, wsd[:nred2], wsd[nred2:],
-                                 n, h * w, cs[0], ACT_NONE, float(eps), in_act)
-                elif (fuse_act and act == ACT_SELU and ctx.gnres[i] is not None and (GN_SUMS & 1) and (cout, cs[i]) == (32, 16) and
-                      k == 3 and pad == 1 and tuple(ctx.gnres[i][0].shape) == tuple(x.shape) and lib.fn('dis_get_conv_split')() == 1):
-                    slots = lib.fn('dis_conv2d_gnsums_slots')()
-                    ab = _zeros_d(n * slots * 2 * cs[i], x.device)
-                    lib.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gy, y, wi, cout, cs[i], wi.stride(0), gx, x, ctx.gnres[i][0], ab,
-                             n, gy.shape[1], gy.shape[2], cout, cs[i], k - 1 - pad)
-                    _GN_PRE[gx.data_ptr()] = (ab, slots)
-                elif fuse_act:
-                    if _bwd_fused_ok(cs[i], cout, k, 1, pad) and lib.fn('dis_get_conv_split')() == 1:
-                        # (ref_conv's 32-channel slice: gy act'(y) feeds the input gradient and the weight gradient in one launch)
-                        gwf = _gw_slice(gw, off, cs[i])
-                        if _bwd_fused(gy, y, None, act, None, wi, gx, False, None, None, None, x, None, gwf,
-                                      gb if (i == 0 and has_bias) else None, n, h, w):
-                            need_w[0] = gwf
-                    if need_w[0] is None:
-                        lib.call('dis_conv2d_dgrad_bf16x3_act', gy, y, act, wi, cout, cs[i], wi.stride(0), gx, n, gy.shape[1],
-                                 gy.shape[2], cout, cs[i], k - 1 - pad, 0)
-                elif lz is not None:   # (i == 0: the token's pass on load, no epilogue)
-                    _, lg, lq, lcoef, lin_act = lz
-                    gpre = torch.empty_like(lg)
-                    if not lib.call_try('dis_conv2d_dgrad_f16x2_gnb', lg, lq, lcoef, lin_act, gpre, wi, cout, cs[i], wi.stride(0), gx, 0,
-                                        None, None, None, n, h, w, cs[i]):
-                        gpre = _gn_lazy_materialize(lz)
-                        _conv_fwd_any(gpre, wi, cs[i], 1, None, gx, None, n, gpre.shape[1], gpre.shape[2], cout, cs[i], k, 1,
-                                      k - 1 - pad, ACT_NONE)
-                    lz = None
-                else:
-                    if _bwd_fused_ok(cs[i], cout, k, 1, pad) and lib.fn('dis_get_conv_split')() == 1:
-                        gwf = _gw_slice(gw, off, cs[i])
-                        if _bwd_fused(gpre, None, None, ACT_NONE, None, wi, gx, False, None, None, None, x, None, gwf,
-                                      gb if (i == 0 and has_bias) else None, n, h, w):
-                            need_w[0] = gwf
-                    if need_w[0] is None:
-                        _conv_fwd_any(gpre, wi, cs[i], 1, None, gx, None, n, gpre.shape[1], gpre.shape[2], cout, cs[i], k, 1,
-                                      k - 1 - pad, ACT_NONE)
-            assert lz is None   # (redeemed by the first source's launch: ctx.lazy_ok guarantees that it has one)
-            gxs.append(gx)
-            if need_w[0] is not None:   # (the fused launch above has written this slice of the weight gradient in place)
-                if not GW_INPLACE:
-                    gw[:, off:off + cs[i]].copy_(need_w[0])
-                need_w[0] = None
-                off += cs[i]
-                continue
-            gwi = torch.empty((cout, cs[i], k, k), dtype=torch.float32, device=x.device)
-            wsz = lib.fn('dis_conv2d_wgrad_workspace')(cs[i], cout, k, 1)
-            if wsz < 0:
-                raise lib.DisHipError(f'conv2d_multi wgrad: unsupported shape cin={cs[i]} cout={cout} k={k}')
-            ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
-            gbi = gb if (i == 0 and has_bias) else None
-            if gn0:
-                lib.call('dis_conv2d_wgrad_bf16x3_gn', x, gn_stats, gn_gamma, ctx.beta_ref, float(gn_meta[0]), gpre, gwi, gbi, ws, n,
-                         h, w, cs[0], cs[0], cout, k, 1, pad)
-            elif fuse_act:
-                lib.call('dis_conv2d_wgrad_bf16x3_act', x, gy, y, act, gwi, gbi, ws, n, h, w, cs[i], cs[i], cout, k, 1, pad)
+            grads = (gw[:, off:off + cs[i]], gb if i == 0 else None)   # (the fused launch writes the slice in place)
+            gx = torch.empty_like(x) if ctx.needs_input_grad[10 + i] else None
+            gnres = ctx.gnres[i]
+            if i == 0 and gn_meta is not None:
+                # gradient wrt the normalised tensor, then through the GroupNorm (as _Conv2dGnIn.backward)
+                eps, in_act = float(gn_meta[0]), gn_meta[1]
+                gnorm = torch.empty_like(x) if gx is not None else None
+                gpre, _, _, gn = _conv_bwd_slice(
+                    wi, x, gnorm, False, grads, pad=pad, lz=lz, gy=gpre, xgn=(gn_stats, gn_gamma, ctx.beta_ref, eps),
+                    sums=(x, None) if GN_SUMS & 8 else None, keep_gpre=True,
+                    after_dgrad=lambda ab, slots: _gn_bwd_after_dgrad(gnorm, x, gn_stats, gn_gamma, ctx.beta_ref, eps, in_act, ab, slots,
+                                                                      ctx.x0_lazy))
+                if gn is not None:
+                    gx, gg_ret, gbt_ret = gn
+            elif (gx is not None and fuse_act and act == ACT_SELU and gnres is not None and (GN_SUMS & 1) and (cout, cs[i]) == (32, 16) and
+                  k == 3 and pad == 1 and tuple(gnres[0].shape) == tuple(x.shape) and lib.fn('dis_get_conv_split')() == 1):
+                # (x = SELU(GroupNorm(.) + res) of a ResNetBlock and this slice is its only consumer: as final_conv in _Conv2d.backward)
+                ab, slots = _gn_sums(n, cs[i], x.device)
+                lib.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gy, y, wi, cout, cs[i], wi.stride(0), gx, x, gnres[0], ab,
+                         n, gy.shape[1], gy.shape[2], cout, cs[i], k - 1 - pad)
+                _GN_PRE[gx.data_ptr()] = (ab, slots)
+                _conv_bwd_slice(wi, x, None, False, grads, pad=pad, gy=gy, act=act, y=y)
             else:
-                _conv_wgrad_any(x, gpre, gwi, gbi, ws, n, h, w, cs[i], cs[i], cout, k, 1, pad)
-            gw[:, off:off + cs[i]].copy_(gwi)  # small strided memory move into the (flat) weight-gradient slice
+                gpre_i = _conv_bwd_slice(wi, x, gx, False, grads, pad=pad, lz=lz, gy=gy if fuse_act else gpre,
+                                         act=act if fuse_act else ACT_NONE, y=y, keep_gpre=True)[0]
+                gpre = gpre if fuse_act else gpre_i
+            lz = None   # (redeemed or materialised by the first source's launch)
+            gxs.append(gx)
             off += cs[i]
         _sinks_written()
         return (gw_ret, gb_ret, None, None, None, None, None, gg_ret, gbt_ret, None) + tuple(gxs)
@@ -1769,11 +1692,7 @@ class _Conv2dScaledIn(torch.autograd.Function):
         ctx.cfg = (stride, pad, bias is not None)
         ctx.bias_ref = bias
         ctx.join = join
-        if want_stats:
-            ctx.mark_non_differentiable(stats)
-            ctx.set_materialize_grads(False)  # no zero tensor for the statistics' (non-existent) gradient
-            return y, stats
-        return y, None
+        return _with_stats(ctx, y, stats)
 
     @staticmethod
     def backward(ctx, gy, _gstats):
@@ -1786,26 +1705,21 @@ class _Conv2dScaledIn(torch.autograd.Function):
         if lz is not None and not (ctx.needs_input_grad[0] and k == 1 and stride == 1 and pad == 0 and (cin, cout) == (128, 32)):
             gy, lz = _gn_lazy_materialize(lz), None
         gx = None
+        join = ctx.join or _SOLE
         if lz is not None:
             _, lg, lq, lcoef, lin_act = lz
-            join = ctx.join
-            second = join is not None and join.buf is not None
-            gx = join.take(x.shape) if second else torch.empty_like(x)
+            gx, second = join.target(x)
             gy = torch.empty_like(lg)
             lib.call('dis_conv2d_dgrad1x1_scaled_gnb', lg, lq, lcoef, lin_act, gy, _pack_w(weight, cin, 1), gx, xscale, n, hin, win,
                      cout, cin, 1 if second else 0)
-            if join is not None and not second:
-                gx = join.first(gx)
+            gx = join.result(gx, second)
         gy = _c(gy)
         if lz is None and ctx.needs_input_grad[0]:
             assert stride == 1
-            join = ctx.join
-            second = join is not None and join.buf is not None
-            gx = join.take(x.shape) if second else torch.empty_like(x)
+            gx, second = join.target(x)
             lib.call('dis_conv2d_fwd_scaled', gy, None, _pack_w(weight, cin, 1), None, gx, xscale, None, n, gy.shape[1],
                      gy.shape[2], cout, cin, k, 1, k - 1 - pad, ACT_NONE | (CONV_ACCUM if second else 0))
-            if join is not None and not second:
-                gx = join.first(gx)
+            gx = join.result(gx, second)
         gw, gw_ret = _sink(weight)
         gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
         wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin, cout, k, stride)
@@ -2368,47 +2282,23 @@ class _GroupNorm(torch.autograd.Function):
         gg, gg_ret = _sink(gamma)
         gb, gb_ret = _sink(ctx.beta_ref)
         pre = _GN_PRE.pop(gy.data_ptr(), None)
-        if pre is not None and not has_res and act == ACT_NONE:
-            # (a plain GroupNorm output with two consumers: the consumer whose backward ran second left the sums of the complete g)
-            ab, slots = pre
-            if ctx.x_lazy and GN_LAZY:
-                gx = _gn_lazy_defer(gy, x, stats, gamma, ab, slots, gg, gb, n, hw, c, eps, in_act, uid=ctx.x_lazy)
-            else:
-                gx = torch.empty_like(x)
-                coef = torch.empty(n * (c + 2) + 4 * n * c + 2, dtype=torch.float32, device=x.device)
-                lib.call('dis_gn_bwd_from_sums', gy, x, stats, gamma, ab, slots, gx, gg, gb, coef, n, hw, c, eps, in_act)
-            _sinks_written()
-            return gx, None, gg_ret, gb_ret, None, None, None, None, None, None, None
-        if pre is not None and has_res and act == ACT_SELU and in_act == ACT_NONE:
-            # gy already IS the gradient wrt the pre-activation value (the producing input-gradient launch multiplied by
-            # SELU'(y) and left the channel sums): it doubles as the residual gradient, and one elementwise pass gives gx
-            ab, slots = pre
-            if ctx.x_lazy and GN_LAZY:
-                gx = _gn_lazy_defer(gy.view(x.shape), x, stats, gamma, ab, slots, gg, gb, n, hw, c, eps, ACT_NONE, uid=ctx.x_lazy)
-            else:
-                gx = torch.empty_like(x)
-                coef = torch.empty(n * (c + 2) + 4 * n * c + 2, dtype=torch.float32, device=x.device)
-                lib.call('dis_gn_bwd_from_sums', gy, x, stats, gamma, ab, slots, gx, gg, gb, coef, n, hw, c, eps, ACT_NONE)
-            gres = gy.view(x.shape)
-            if ctx.join is not None:
-                if ctx.join.buf is None:
-                    gres = ctx.join.first(gres)
-                else:
-                    gres = ctx.join.take(gres.shape).add_(gres)
-            _sinks_written()
-            return gx, None, gg_ret, gb_ret, gres, None, None, None, None, None, None
-        if pre is not None:
+        if pre is not None and ((not has_res and act == ACT_NONE) or (has_res and act == ACT_SELU and in_act == ACT_NONE)):
+            # the consumer whose backward ran second left the sums of the complete g: a plain GroupNorm output with two consumers,
+            # or (residual + SELU) gy already IS the gradient wrt the pre-activation value (the producing input-gradient launch
+            # multiplied by SELU'(y)), which doubles as the residual gradient, and one elementwise pass gives gx
+            gx = _gn_bwd_from_sums(gy, x, stats, gamma, pre[0], pre[1], gg, gb, eps, in_act, ctx.x_lazy)
+            gres = gy.view(x.shape) if has_res else None
+        elif pre is not None:
             # the producer has ALREADY turned gy into the pre-activation gradient and formed its channel sums: the generic
             # two-pass form below would apply act' a second time.  No networks here reach this; a new caller must not do so silently.
             raise RuntimeError(f'group_norm backward: channel sums were registered for this gradient but no from-sums form matches '
                                f'(residual={has_res}, act={act}, in_act={in_act})')
-        if (ctx.x_lazy and GN_LAZY and GN_RES_SUMS and c in (16, 32) and x.dim() == 4 and (act == ACT_NONE or has_res) and
+        elif (ctx.x_lazy and GN_LAZY and GN_RES_SUMS and c in (16, 32) and x.dim() == 4 and (act == ACT_NONE or has_res) and
                 (in_act == ACT_NONE or act == ACT_NONE) and lib.fn('dis_get_conv_split')() == 1):
             # nobody left channel sums for this gradient (it comes from a join, a resize, a feature warp), but the producer of x
             # redeems tokens: ONE pass forms g = gy act'(y) (the residual gradient, stored), and the sums of g and g x; the
             # elementwise pass rides on the producer's input-gradient launch (instead of a reduce and an apply launch over gy, y, x)
-            slots = lib.fn('dis_conv2d_gnsums_slots')()
-            ab = _zeros_d(n * slots * 2 * c, x.device)
+            ab, slots = _gn_sums(n, c, x.device)
             gres = torch.empty_like(x) if (has_res or act != ACT_NONE) else None
             lib.call('dis_gn_bwd_res_sums', gy, y, x, gres, ab, slots, n, hw, c, act)
             g_ = gres if gres is not None else gy.view(x.shape)
@@ -2416,13 +2306,8 @@ class _GroupNorm(torch.autograd.Function):
             if not has_res:
                 gres = None
         else:
-            gx = torch.empty_like(x)
             gres = torch.empty_like(x) if has_res else None
-            wtot = lib.fn('dis_gn_bwd_workspace')(n, c)
-            ws = torch.empty(wtot, dtype=torch.float64, device=x.device)
-            nred2 = wtot // (2 + 2 * c) * 2  # (n * blocks-per-sample-max) pairs of per-block sums, then the parameter partials
-            red, pacc = ws[:nred2], ws[nred2:]
-            lib.call('dis_gn_apply_bwd', gy, y, x, stats, gamma, gx, gres, gg, gb, red, pacc, n, hw, c, act, eps, in_act)
+            gx = _gn_apply_bwd(gy, y, x, stats, gamma, gres, gg, gb, act, eps, in_act)
         if gres is not None and ctx.join is not None:
             if ctx.join.buf is None:
                 gres = ctx.join.first(gres)
@@ -2501,8 +2386,7 @@ class _GatherWarpedFeat(torch.autograd.Function):
                 # this launch completes the gradient wrt y = SELU(GroupNorm(x2) + residual): it stores g SELU'(y) and leaves the channel
                 # sums of the GroupNorm's backward (_GroupNorm.backward finds them: no pass over g, y, x2 of its own)
                 y, x2 = ctx.saved_tensors[2:4]
-                slots = lib.fn('dis_conv2d_gnsums_slots')()
-                ab = _zeros_d(tl * bs * slots * 2 * c, g.device)
+                ab, slots = _gn_sums(tl * bs, c, g.device)
                 if lib.call_try('dis_gather_warped_feat_bwd_csr_gnres', _c(g), csr, init, gf, y, x2, ab, slots, ACT_SELU, tl, bs, h, w, c):
                     _GN_PRE[gf.data_ptr()] = (ab, slots)
                     done = True
@@ -2570,13 +2454,10 @@ class _MaskWeightSlots(torch.autograd.Function):
         (geom,) = ctx.saved_tensors
         g = _c(g)
         tl, bs, h, w, s, c = g.shape
-        join = ctx.join
-        second = join is not None and join.buf is not None
-        out = join.take(g.shape) if second else torch.empty_like(g)
+        join = ctx.join or _SOLE
+        out, second = join.target(g)
         lib.call('dis_mask_weight_slots', g, geom, out, tl * bs * h * w, s, c, 1 if second else 0)
-        if join is not None and not second:
-            out = join.first(out)
-        return out, None, None
+        return join.result(out, second), None, None
 
 
 def mask_weight_slots(wf, geom, join=None):
@@ -2652,19 +2533,17 @@ class _Conv3dKnn(torch.autograd.Function):
     def backward(ctx, gy):
         geom, wf, d1w, d1b, d2w, d2b, w, idx, y, agg = ctx.saved_tensors
         tl, bs, h, wd, s, c = wf.shape
-        join = ctx.join
-        second = join is not None and join.buf is not None
+        join = ctx.join or _SOLE
         sunk = _sink_block((w, d1w, d1b, d2w, d2b))  # the kernel's parameter-gradient block IS the flat buffer's order
         gp = sunk if sunk is not None else torch.empty(1632, dtype=torch.float32, device=wf.device)
         if agg is not None:
             # class-ordered read-modify-write (det) / one launch with float atomics (agg): both ADD to the rows
-            gwf = join.take(wf.shape) if second else torch.zeros_like(wf)
+            gwf, second = join.target(wf, torch.zeros_like)
             acc = torch.empty(lib.fn('dis_conv3d_knn_bwd_det_workspace')(tl, bs, h, wd, ctx.stride), dtype=torch.float32,
                               device=wf.device)
             lib.call('dis_conv3d_knn_bwd_det' if CONV3D_BWD == 'det' else 'dis_conv3d_knn_bwd_agg', geom, wf, d1w, d1b, d2w, d2b, w,
                      idx, y, agg, _c(gy), gwf, gp, acc, tl, bs, h, wd, ctx.stride)
-            if join is not None and not second:
-                gwf = join.first(gwf)
+            gwf = join.result(gwf, second)
             _sinks_written()
             if sunk is not None:
                 return (None, gwf, None, None, None, None, None, None, None, None)
@@ -2673,17 +2552,16 @@ class _Conv3dKnn(torch.autograd.Function):
         acc = torch.empty(lib.fn('dis_conv3d_knn_bwd_workspace')(), dtype=torch.float32, device=wf.device)
         if ctx.c3csr is not None:
             # deterministic form: per-entry gradient rows staged, then summed per source row in list order
-            gwf = join.take(wf.shape) if second else torch.empty_like(wf)
+            gwf, second = join.target(wf)
             stage = torch.empty(lib.fn('dis_conv3d_knn_bwd_stage')(tl, bs, h, wd, ctx.stride), dtype=torch.float32,
                                 device=wf.device)
             lib.call('dis_conv3d_knn_bwd_csr', geom, wf, d1w, d1b, d2w, d2b, w, idx, y, _c(gy), gwf, gp, acc, ctx.c3csr,
                      stage, 1 if second else 0, tl, bs, h, wd, ctx.stride)
         else:
-            gwf = join.take(wf.shape) if second else torch.zeros_like(wf)  # the scatter accumulates (float atomics)
+            gwf, second = join.target(wf, torch.zeros_like)  # the scatter accumulates (float atomics)
             lib.call('dis_conv3d_knn_bwd', geom, wf, d1w, d1b, d2w, d2b, w, idx, y, _c(gy), gwf, gp, acc, tl, bs, h, wd,
                      ctx.stride)
-        if join is not None and not second:
-            gwf = join.first(gwf)
+        gwf = join.result(gwf, second)
         _sinks_written()
         if sunk is not None:
             return (None, gwf, None, None, None, None, None, None, None, None)
