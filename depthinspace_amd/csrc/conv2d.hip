@@ -484,6 +484,10 @@ static int dispatch_conv(const ConvArgs& a, int cin, int cout, int kh, int kw, i
   CONV_CASE(32, 96, 3, 3, 1)
   CONV_CASE(128, 32, 1, 1, 1)
   CONV_CASE(32, 128, 1, 1, 1)
+  CONV_CASE(64, 32, 1, 1, 1)    // conv_mf at track lengths 2 and 3 (32 tl -> 32) and its input gradient
+  CONV_CASE(32, 64, 1, 1, 1)
+  CONV_CASE(96, 32, 1, 1, 1)
+  CONV_CASE(32, 96, 1, 1, 1)
   CONV_CASE(32, 32, 4, 4, 2)
   CONV_CASE(32, 32, 2, 2, 1)
   return DIS_ERR_UNSUPPORTED;
@@ -2511,6 +2515,8 @@ static int dispatch_wgrad(const WgArgs& a, float* gw, float* gb, int cin_real, i
   WG_CASE(48, 32, 3, 1)
   WG_CASE(96, 32, 3, 1)
   WG_CASE(128, 32, 1, 1)
+  WG_CASE(64, 32, 1, 1)
+  WG_CASE(96, 32, 1, 1)
   if (cin == 32 && cout == 32 && k == 4 && stride == 2) return launch_wgrad_k4s2(a, gw, gb, cin_real, s);
   WG_CASE(4, 32, 7, 2)   // DispNetS conv1 (2 -> 32, k7 s2): all 49 taps in one pass over the pixels
   return DIS_ERR_UNSUPPORTED;
@@ -2548,6 +2554,8 @@ extern "C" long dis_conv2d_wgrad_workspace(int cin, int cout, int k, int stride)
   WS_CASE(48, 32, 3, 1)
   WS_CASE(96, 32, 3, 1)
   WS_CASE(128, 32, 1, 1)
+  WS_CASE(64, 32, 1, 1)
+  WS_CASE(96, 32, 1, 1)
   WS_CASE(32, 32, 4, 2)
   WS_CASE(4, 32, 7, 2)
   return -1;

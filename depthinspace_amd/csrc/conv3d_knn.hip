@@ -1,9 +1,11 @@
 // Conv3D: k-nearest-neighbour continuous convolution over the 3x3xTL candidate window
 // (reference model/multi_frame_networks.py:432-512), for all target frames of a step in one launch.
 //
-// Data layout is built for this gather: geom (tl,bs,h,w,tl,4) keeps xyz+mask of the 4 slots of a pixel
-// in one 64-B line, wf (tl,bs,h,w,tl,32) keeps each slot's 32 features in one 128-B line.
-//   kernel 1 (select):    one lane per output pixel: 36 keys, masked top-9 exactly as torch.topk picks them
+// Data layout is built for this gather: geom (tl,bs,h,w,tl,4) keeps xyz+mask of the tl slots of a pixel
+// in one line (64 B at tl = 4), wf (tl,bs,h,w,tl,32) keeps each slot's 32 features in one 128-B line.
+// Every kernel that addresses slots is instanced per track length TL in {2, 3, 4} (the reference's --track_length);
+// the host entry points dispatch on their `tl` argument and reject any other value.
+//   kernel 1 (select):    one lane per output pixel: 9 TL keys, masked top-9 exactly as torch.topk picks them
 //   kernel 2 (forward):   one wave per group of 16 output pixels.  Every per-pixel matrix product (dense2 16->32 per
 //                         neighbour, the 32x32 mix) runs on the matrix cores (v_mfma_f32_16x16x4_f32) in a
 //                         "pixel on the lane" layout: lane (li,lg) owns pixel li and channels {16*mt + 4*lg + r},
@@ -17,39 +19,41 @@
 #include "common.h"
 #include "nth_select.h"
 #include <float.h>
+#include <type_traits>
 
-#define C3_TL 4
 #define C3_NB 9
 #define C3_C 32
 #define C3_H1 16
-#define C3_NCAND (9 * C3_TL)
 
 struct C3Dims {
   int tl, bs, h, w, ho, wo, stride;
 };
 
-// One lane per output pixel.  The 36 keys are the reference's, operation for operation (multi_frame_networks.py:490-497:
+// One lane per output pixel.  The 9 TL keys are the reference's, operation for operation (multi_frame_networks.py:490-497:
 // plane = xyz / (z + 1e-12), squared distance to candidate 16 summed x, y, z; -ffp-contract=off keeps every rounding),
 // and the 9 neighbours are the ones torch.topk(largest=False, sorted=False) returns on the CPU, in its order: ATen runs
 // std::nth_element on the (key, id) row, restated in nth_select.h, so tied keys (masked candidates all share one fill
-// value; equidistant planar candidates) resolve exactly as in the reference.
+// value; equidistant planar candidates) resolve exactly as in the reference.  (ATen takes that path whenever k * 64 > n: for
+// k = 9 at every n = 9 TL up to 36.)
 #define C3_SEL_T 64
 struct C3SelView {
   NthPair* base;
   __device__ __forceinline__ NthPair& operator[](int i) const { return base[i * C3_SEL_T]; }
 };
+template <int TL>
 __global__ __launch_bounds__(C3_SEL_T) void conv3d_select_kernel(const float4* __restrict__ geom,
                                                                  unsigned char* __restrict__ idx, C3Dims d) {
-  __shared__ NthPair sq[C3_NCAND * C3_SEL_T];
+  constexpr int NCAND = 9 * TL;
+  __shared__ NthPair sq[NCAND * C3_SEL_T];
   const C3SelView q{sq + threadIdx.x};
   const long total = (long)d.tl * d.bs * d.ho * d.wo;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int ox = (int)(i % d.wo);
     const int oy = (int)((i / d.wo) % d.ho);
     const long tb = i / ((long)d.wo * d.ho);
-    const float4* g = geom + tb * d.h * d.w * C3_TL;
+    const float4* g = geom + tb * d.h * d.w * TL;
     const int cy = oy * d.stride, cx = ox * d.stride;
-    const float4 ctr = g[((long)cy * d.w + cx) * C3_TL];
+    const float4 ctr = g[((long)cy * d.w + cx) * TL];
     const float cden = ctr.z + 1e-12f;
     const float pcx = ctr.x / cden, pcy = ctr.y / cden, pcz = ctr.z / cden;
     for (int ky = 0; ky < 3; ++ky) {
@@ -58,20 +62,20 @@ __global__ __launch_bounds__(C3_SEL_T) void conv3d_select_kernel(const float4* _
         const int ix = cx - 1 + kx;
         const bool inb = iy >= 0 && iy < d.h && ix >= 0 && ix < d.w;
 #pragma unroll
-        for (int s = 0; s < C3_TL; ++s) {
+        for (int s = 0; s < TL; ++s) {
           float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);  // zero padding: xyz = 0, mask = 0
-          if (inb) qv = g[((long)iy * d.w + ix) * C3_TL + s];
+          if (inb) qv = g[((long)iy * d.w + ix) * TL + s];
           const float den = qv.z + 1e-12f;
           const float dx = qv.x / den - pcx, dy = qv.y / den - pcy, dz = qv.z / den - pcz;
           float key = (dx * dx + dy * dy) + dz * dz;
           // masked: the reference fills max(dist) + 1, one value above every valid key; FLT_MAX orders the same way
           if (!(qv.w > 0.5f)) key = FLT_MAX;
-          const int id = (ky * 3 + kx) * C3_TL + s;
+          const int id = (ky * 3 + kx) * TL + s;
           q[id] = NthPair{key, id};
         }
       }
     }
-    nth_element_pairs(q, C3_NCAND, C3_NB - 1);
+    nth_element_pairs(q, NCAND, C3_NB - 1);
 #pragma unroll
     for (int k = 0; k < C3_NB; ++k) idx[i * C3_NB + k] = (unsigned char)q[k].id;
   }
@@ -127,6 +131,7 @@ struct C3Nb {
   float lx, ly, lz;
   long foff;
 };
+template <int TL>
 __device__ __forceinline__ C3Nb c3_neighbor(const float4* __restrict__ geom, const unsigned char* __restrict__ idx,
                                             const C3Dims& d, long i, int n, bool pv, int oy, int ox, long tb,
                                             const float4& ctr) {
@@ -135,10 +140,10 @@ __device__ __forceinline__ C3Nb c3_neighbor(const float4* __restrict__ geom, con
   r.foff = -1;
   if (pv) {
     const int id = idx[i * C3_NB + n];
-    const int tap = id / C3_TL, slot = id % C3_TL;
+    const int tap = id / TL, slot = id % TL;
     const int iy = oy * d.stride - 1 + tap / 3, ix = ox * d.stride - 1 + tap % 3;
     if (iy >= 0 && iy < d.h && ix >= 0 && ix < d.w) {
-      const long e = (tb * d.h * d.w + (long)iy * d.w + ix) * C3_TL + slot;
+      const long e = (tb * d.h * d.w + (long)iy * d.w + ix) * TL + slot;
       q = geom[e];
       r.foff = e * C3_C;
     }
@@ -152,6 +157,7 @@ __device__ __forceinline__ C3Nb c3_neighbor(const float4* __restrict__ geom, con
 // The neighbour of (pixel, n) is found through two dependent loads (selection index -> geometry); the feature row is a
 // third.  Building the 9 x 16 descriptors of a group once, three per lane with all chains in flight together, and
 // reading them back from LDS takes those chains out of the per-neighbour loops (the kernels are latency-bound there).
+template <int TL>
 __device__ __forceinline__ void c3_build_desc(float4* D, const float4* __restrict__ geom,
                                               const unsigned char* __restrict__ idx, const C3Dims& d, long ic, bool pv,
                                               int oy, int ox, long tb, const float4& ctr, int li, int lg) {
@@ -159,7 +165,7 @@ __device__ __forceinline__ void c3_build_desc(float4* D, const float4* __restric
   for (int k = 0; k < 3; ++k) {
     const int n = lg + 4 * k;
     if (n < C3_NB) {
-      const C3Nb nb = c3_neighbor(geom, idx, d, ic, n, pv, oy, ox, tb, ctr);
+      const C3Nb nb = c3_neighbor<TL>(geom, idx, d, ic, n, pv, oy, ox, tb, ctr);
       D[n * C3_GP + li] = make_float4(nb.lx, nb.ly, nb.lz, __int_as_float(nb.foff >= 0 ? (int)(nb.foff / C3_C) : -1));
     }
   }
@@ -217,6 +223,7 @@ __device__ __forceinline__ void c3_mlp(const float* w2s, const C3Lane& Q, const 
     for (int r = 0; r < 4; ++r) h2[mt][r] = selu_f(pre[mt][r] + Q.b2[mt][r]);
 }
 
+template <int TL>
 __global__ __launch_bounds__(256) void conv3d_fwd_kernel(const float4* __restrict__ geom, const float* __restrict__ wf,
                                                           C3Params P, const unsigned char* __restrict__ idx,
                                                           float* __restrict__ y, C3Dims d, float* __restrict__ agg_out) {
@@ -239,9 +246,9 @@ __global__ __launch_bounds__(256) void conv3d_fwd_kernel(const float4* __restric
     const long ic = pv ? i : total - 1;
     const int ox = (int)(ic % d.wo), oy = (int)((ic / d.wo) % d.ho);
     const long tb = ic / ((long)d.wo * d.ho);
-    const float4 ctr = geom[(tb * d.h * d.w + (long)(oy * d.stride) * d.w + ox * d.stride) * C3_TL];
+    const float4 ctr = geom[(tb * d.h * d.w + (long)(oy * d.stride) * d.w + ox * d.stride) * TL];
     f32x4 agg[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-    c3_build_desc(L.D[wave], geom, idx, d, ic, pv, oy, ox, tb, ctr, Q.li, Q.lg);
+    c3_build_desc<TL>(L.D[wave], geom, idx, d, ic, pv, oy, ox, tb, ctr, Q.li, Q.lg);
 #pragma unroll 3
     for (int n = 0; n < C3_NB; ++n) {
       const C3Nb nb = c3_desc(L.D[wave], n, Q.li);
@@ -290,6 +297,7 @@ __device__ __forceinline__ float c3_sum16(float v) {
   return v;
 }
 
+template <int TL>
 __global__ __launch_bounds__(256, 2) void conv3d_bwd_kernel(const float4* __restrict__ geom,
                                                               const float* __restrict__ wf, C3Params P,
                                                               const unsigned char* __restrict__ idx,
@@ -331,11 +339,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_bwd_kernel(const float4* __rest
     const long ic = pv ? i : total - 1;
     const int ox = (int)(ic % d.wo), oy = (int)((ic / d.wo) % d.ho);
     const long tb = ic / ((long)d.wo * d.ho);
-    const float4 ctr = geom[(tb * d.h * d.w + (long)(oy * d.stride) * d.w + ox * d.stride) * C3_TL];
+    const float4 ctr = geom[(tb * d.h * d.w + (long)(oy * d.stride) * d.w + ox * d.stride) * TL];
     // ---- recompute the forward aggregate (h1/h2 are recomputed again per neighbour below: cheaper than holding
     //      72 registers of h2 across the group, which spilled and halved the occupancy)
     f32x4 agg[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-    c3_build_desc(L.D[wave], geom, idx, d, ic, pv, oy, ox, tb, ctr, Q.li, Q.lg);
+    c3_build_desc<TL>(L.D[wave], geom, idx, d, ic, pv, oy, ox, tb, ctr, Q.li, Q.lg);
 #pragma unroll 3
     for (int n = 0; n < C3_NB; ++n) {
       const C3Nb nb = c3_desc(L.D[wave], n, Q.li);
@@ -533,8 +541,18 @@ __global__ __launch_bounds__(256) void c3_param_reduce_kernel(const float* __res
 
 #define C3_BWD_BLOCKS 512
 
+// The instanced track lengths.  c3_with_tl(tl, f) calls f(std::integral_constant<int, TL>) for the caller's tl, which c3_dims
+// has checked to be one of them.
+static bool c3_tl_ok(int tl) { return tl == 2 || tl == 3 || tl == 4; }
+template <class F>
+static void c3_with_tl(int tl, F&& f) {
+  if (tl == 2) f(std::integral_constant<int, 2>{});
+  else if (tl == 3) f(std::integral_constant<int, 3>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
 static int c3_dims(C3Dims* d, int tl, int bs, int h, int w, int stride) {
-  if (tl != C3_TL) return DIS_ERR_UNSUPPORTED;
+  if (!c3_tl_ok(tl)) return DIS_ERR_UNSUPPORTED;
   if (bs <= 0 || h <= 0 || w <= 0) return DIS_ERR_BAD_SHAPE;
   if (stride != 1 && stride != 2) return DIS_ERR_UNSUPPORTED;
   d->tl = tl; d->bs = bs; d->h = h; d->w = w; d->stride = stride;
@@ -550,8 +568,10 @@ extern "C" int dis_conv3d_knn_select(const float* geom, unsigned char* idx_out, 
   int rc = c3_dims(&d, tl, bs, h, wd, stride);
   if (rc != DIS_OK) return rc;
   const long total = (long)tl * bs * d.ho * d.wo;
-  hipLaunchKernelGGL(conv3d_select_kernel, dim3(dis_ew_grid(total, C3_SEL_T)), dim3(C3_SEL_T), 0, (hipStream_t)stream,
-                     (const float4*)geom, idx_out, d);
+  c3_with_tl(tl, [&](auto T) {
+    hipLaunchKernelGGL(conv3d_select_kernel<decltype(T)::value>, dim3(dis_ew_grid(total, C3_SEL_T)), dim3(C3_SEL_T), 0,
+                       (hipStream_t)stream, (const float4*)geom, idx_out, d);
+  });
   DIS_CHECK_LAUNCH();
   return DIS_OK;
 }
@@ -569,7 +589,10 @@ extern "C" int dis_conv3d_knn_fwd_agg(const float* geom, const float* wf, const 
   C3Params P{dense1_w, dense1_b, dense2_w, dense2_b, w};
   int grid = dis_cdiv(dis_cdiv(total, C3_GP), 4);
   if (grid > 1024) grid = 1024;
-  hipLaunchKernelGGL(conv3d_fwd_kernel, dim3(grid), dim3(256), 0, s, (const float4*)geom, wf, P, idx, y, d, agg);
+  c3_with_tl(tl, [&](auto T) {
+    hipLaunchKernelGGL(conv3d_fwd_kernel<decltype(T)::value>, dim3(grid), dim3(256), 0, s, (const float4*)geom, wf, P, idx, y, d,
+                       agg);
+  });
   DIS_CHECK_LAUNCH();
   return DIS_OK;
 }
@@ -651,10 +674,12 @@ static int c3_bwd_run(const float* geom, const float* wf, const float* dense1_w,
   C3Params P{dense1_w, dense1_b, dense2_w, dense2_b, w};
   int grid = dis_cdiv(dis_cdiv(total, C3_GP), 4);
   if (grid > C3_BWD_BLOCKS) grid = C3_BWD_BLOCKS;
-  hipLaunchKernelGGL(conv3d_bwd_kernel, dim3(grid), dim3(256), 0, s, (const float4*)geom, wf, P, idx, y, gy, grad_wf,
-                     workspace, d, stage);
+  c3_with_tl(tl, [&](auto T) {
+    hipLaunchKernelGGL(conv3d_bwd_kernel<decltype(T)::value>, dim3(grid), dim3(256), 0, s, (const float4*)geom, wf, P, idx, y, gy,
+                       grad_wf, workspace, d, stage);
+  });
   if (csr) {
-    const long nsrc = (long)tl * bs * h * wd * C3_TL;
+    const long nsrc = (long)tl * bs * h * wd * tl;
     hipLaunchKernelGGL(conv3d_feat_gather_kernel, dim3(dis_ew_grid(nsrc * 8, 256)), dim3(256), 0, s, (const float*)stage, csr,
                        csr + 2 * nsrc + 1, grad_wf, nsrc, accumulate);
   }
@@ -767,7 +792,7 @@ union C3DShared {
   C3Lds2 L;
   float red[4][C3_NPARAM];      // (end of the kernel only: aliases the working tiles)
 };
-template <bool CLS>
+template <int TL, bool CLS>
 __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4* __restrict__ geom, const float* __restrict__ wf,
                                                               C3Params P, const unsigned char* __restrict__ idx,
                                                               const float* __restrict__ y, const float* __restrict__ aggp,
@@ -827,8 +852,8 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
   const int total = d.tl * d.bs * ny * nx;
   const int ngroups = (total + C3_GP - 1) / C3_GP;
   const int hw = d.h * d.w;
-  const __amdgpu_buffer_rsrc_t wf_rs = bx_rsrc(wf, (unsigned)d.tl * d.bs * hw * (C3_TL * C3_C * 4u));
-  const __amdgpu_buffer_rsrc_t gwf_rs = bx_rsrc(gwf, (unsigned)d.tl * d.bs * hw * (C3_TL * C3_C * 4u));
+  const __amdgpu_buffer_rsrc_t wf_rs = bx_rsrc(wf, (unsigned)d.tl * d.bs * hw * (TL * C3_C * 4u));
+  const __amdgpu_buffer_rsrc_t gwf_rs = bx_rsrc(gwf, (unsigned)d.tl * d.bs * hw * (TL * C3_C * 4u));
   // ---- one group ahead: the selection ids of a group's pixels.  ids -> {neighbour geometry, feature rows, gradient rows} were two
   // DEPENDENT global round trips in front of everything else a group does (a wave has ~3 groups per launch and one partner wave on
   // its SIMD: nothing hid them).  The next group's ids are requested before the neighbour loop of the current one - unconditionally
@@ -863,7 +888,7 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
   for (int grp = blockIdx.x * 4 + wave; grp < ngroups; grp += gstep) {
     const bool pv = pvN;
     const int i = iN, oy = oyN, ox = oxN, tb = tbN;
-    const float4 ctr = geom[(long)(tb * hw + oy * d.stride * d.w + ox * d.stride) * C3_TL];
+    const float4 ctr = geom[(long)(tb * hw + oy * d.stride * d.w + ox * d.stride) * TL];
     // ---- rows of the 9 neighbours (lane (li, lg): neighbours lg, lg + 4, lg + 8 of pixel li), then their geometry
     int myrow[3];
     float4 qn[3];
@@ -873,9 +898,10 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
       myrow[k] = -1;
       if (n < C3_NB && pv) {
         const unsigned id = idN[k];
-        const unsigned tap = id >> 2, slot = id & 3, ty = (tap * 11u) >> 5;   // (C3_TL = 4; tap / 3 for tap < 9)
+        // (unsigned division by the constant TL: a shift and a mask at TL = 4; (tap * 11) >> 5 = tap / 3 for tap < 9)
+        const unsigned tap = id / (unsigned)TL, slot = id % (unsigned)TL, ty = (tap * 11u) >> 5;
         const int iy = oy * d.stride - 1 + (int)ty, ix = ox * d.stride - 1 + (int)(tap - 3 * ty);
-        if ((unsigned)iy < (unsigned)d.h && (unsigned)ix < (unsigned)d.w) myrow[k] = (tb * hw + iy * d.w + ix) * C3_TL + (int)slot;
+        if ((unsigned)iy < (unsigned)d.h && (unsigned)ix < (unsigned)d.w) myrow[k] = (tb * hw + iy * d.w + ix) * TL + (int)slot;
       }
       if (n < C3_NB) R[n * C3_GP + Q.li] = myrow[k];
     }
@@ -1157,11 +1183,11 @@ static int c3_bwd2_run(bool det, const float* geom, const float* wf, const float
   C3Dims d;
   int rc = c3_dims(&d, tl, bs, h, wd, stride);
   if (rc != DIS_OK) return rc;
-  if ((long)tl * bs * h * wd * C3_TL >= (1L << 31)) return DIS_ERR_BAD_SHAPE;  // (row indices are ints)
+  if ((long)tl * bs * h * wd * tl >= (1L << 31)) return DIS_ERR_BAD_SHAPE;  // (row indices are ints)
   // wf / grad_wf are addressed through ONE buffer descriptor each, 32-bit byte offsets, and BX_OOB (2 GiB) is the offset that
   // drops a lane: past 2 GiB the drop offset would land INSIDE the tensor (padded candidates would load real rows and, in the
   // class-ordered form, store into one).  Same bound as the conv launchers; the caller's alternative is dis_conv3d_knn_bwd.
-  if ((long)tl * bs * h * wd * C3_TL * C3_C * 4L >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
+  if ((long)tl * bs * h * wd * tl * C3_C * 4L >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   C3Params P{dense1_w, dense1_b, dense2_w, dense2_b, w};
   int grids[9], tot;
@@ -1172,14 +1198,18 @@ static int c3_bwd2_run(bool det, const float* geom, const float* wf, const float
     for (int cy = 0; cy < cn; ++cy)
       for (int cx = 0; cx < cn; ++cx, ++k) {
         if (grids[k] == 0) continue;
-        hipLaunchKernelGGL(conv3d_bwd2_kernel<true>, dim3(grids[k]), dim3(256), 0, s, (const float4*)geom, wf, P, idx, y, agg, gy,
-                           grad_wf, workspace + (long)base * C3_NPARAM, d, cn, cy, cx);
+        c3_with_tl(tl, [&](auto T) {
+          hipLaunchKernelGGL((conv3d_bwd2_kernel<decltype(T)::value, true>), dim3(grids[k]), dim3(256), 0, s, (const float4*)geom, wf,
+                             P, idx, y, agg, gy, grad_wf, workspace + (long)base * C3_NPARAM, d, cn, cy, cx);
+        });
         base += grids[k];
       }
   } else {
     tot = c3d_grids(d, tl, bs, 1, grids);
-    hipLaunchKernelGGL(conv3d_bwd2_kernel<false>, dim3(tot), dim3(256), 0, s, (const float4*)geom, wf, P, idx, y, agg, gy, grad_wf,
-                       workspace, d, 1, 0, 0);
+    c3_with_tl(tl, [&](auto T) {
+      hipLaunchKernelGGL((conv3d_bwd2_kernel<decltype(T)::value, false>), dim3(tot), dim3(256), 0, s, (const float4*)geom, wf, P, idx,
+                         y, agg, gy, grad_wf, workspace, d, 1, 0, 0);
+    });
   }
   float* mid = workspace + (long)(tot > C3D_CAP ? tot : C3D_CAP) * C3_NPARAM;
   hipLaunchKernelGGL(c3d_reduce1_kernel, dim3(C3D_NCH, C3D_RS), dim3(256), 0, s, (const float*)workspace, mid, tot);

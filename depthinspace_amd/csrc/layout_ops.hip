@@ -1096,21 +1096,22 @@ extern "C" int dis_gather_csr_build(const float* flows, int* csr, int tl, int bs
   return DIS_OK;
 }
 // ---- CSR of the Conv3D neighbour sets by SOURCE row (deterministic feature gradient, conv3d_knn.hip) ----
-// entry = output pixel * 9 + neighbour; its source row = ((tb * h + iy) * w + ix) * 4 + slot with (tap, slot) = (id / 4, id % 4)
+// entry = output pixel * 9 + neighbour; its source row = ((tb * h + iy) * w + ix) * tl + slot with (tap, slot) = (id / tl, id % tl)
 // of the selected candidate id and (iy, ix) = (oy, ox) * stride - 1 + (tap / 3, tap % 3), as c3_neighbor() computes it.
 // csr = [offsets: nsrc + 1][cursor: nsrc][entries: nent][scan scratch], lists sorted by entry id.
+template <int TL>
 __global__ void c3csr_count_fill_kernel(const unsigned char* __restrict__ idx, int* __restrict__ cursor,
                                         int* __restrict__ entries, long nent, int ho, int wo, int h, int w, int stride,
                                         int fill) {
   for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < nent; e += (long)gridDim.x * blockDim.x) {
     const long i = e / 9;
     const int id = idx[e];
-    const int tap = id >> 2, slot = id & 3;
+    const int tap = id / TL, slot = id % TL;
     const int ox = (int)(i % wo), oy = (int)((i / wo) % ho);
     const long tb = i / ((long)wo * ho);
     const int iy = oy * stride - 1 + tap / 3, ix = ox * stride - 1 + tap % 3;
     if (iy < 0 || iy >= h || ix < 0 || ix >= w) continue;
-    const long src = ((tb * h + iy) * w + ix) * 4 + slot;
+    const long src = ((tb * h + iy) * w + ix) * TL + slot;
     const int pos = atomicAdd(cursor + src, 1);
     if (fill) entries[pos] = (int)e;
   }
@@ -1145,10 +1146,11 @@ __global__ void c3csr_sort_kernel(const int* __restrict__ offsets, int* __restri
   }
 }
 static int c3csr_dims(int tl, int bs, int h, int w, int stride, long* nsrc, long* nent, int* ho, int* wo) {
-  if (tl != 4 || bs <= 0 || h <= 0 || w <= 0 || (stride != 1 && stride != 2)) return DIS_ERR_BAD_SHAPE;
+  // (tl: the track lengths conv3d_knn.hip is instanced for)
+  if (tl < 2 || tl > 4 || bs <= 0 || h <= 0 || w <= 0 || (stride != 1 && stride != 2)) return DIS_ERR_BAD_SHAPE;
   *ho = (h + 2 - 3) / stride + 1;
   *wo = (w + 2 - 3) / stride + 1;
-  *nsrc = (long)tl * bs * h * w * 4;
+  *nsrc = (long)tl * bs * h * w * tl;
   *nent = (long)tl * bs * *ho * *wo * 9;
   if (*nsrc >= 2147483647L || *nent >= 2147483647L) return DIS_ERR_UNSUPPORTED;
   return DIS_OK;
@@ -1175,11 +1177,12 @@ extern "C" int dis_conv3d_csr_build(const unsigned char* idx, int* csr, int tl, 
   hipLaunchKernelGGL(csr_zero_kernel, dim3(dis_ew_grid(nsrc, 256)), dim3(256), 0, s, cursor, nsrc);
   int grid = dis_cdiv(nent, 256);
   if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(c3csr_count_fill_kernel, dim3(grid), dim3(256), 0, s, idx, cursor, entries, nent, ho, wo, h, w, stride, 0);
+  auto count_fill = tl == 2 ? c3csr_count_fill_kernel<2> : tl == 3 ? c3csr_count_fill_kernel<3> : c3csr_count_fill_kernel<4>;
+  hipLaunchKernelGGL(count_fill, dim3(grid), dim3(256), 0, s, idx, cursor, entries, nent, ho, wo, h, w, stride, 0);
   hipLaunchKernelGGL(csr_scan1_kernel, dim3(nblk), dim3(256), 0, s, (const int*)cursor, bsum, nsrc);
   hipLaunchKernelGGL(csr_scan2_kernel, dim3(1), dim3(64), 0, s, bsum, nblk);
   hipLaunchKernelGGL(csr_scan3_kernel, dim3(nblk), dim3(256), 0, s, cursor, offsets, (const int*)bsum, nsrc, nblk);
-  hipLaunchKernelGGL(c3csr_count_fill_kernel, dim3(grid), dim3(256), 0, s, idx, cursor, entries, nent, ho, wo, h, w, stride, 1);
+  hipLaunchKernelGGL(count_fill, dim3(grid), dim3(256), 0, s, idx, cursor, entries, nent, ho, wo, h, w, stride, 1);
   hipLaunchKernelGGL(c3csr_sort_kernel, dim3(dis_ew_grid(nsrc, 256)), dim3(256), 0, s, (const int*)offsets, entries, nsrc);
   DIS_CHECK_LAUNCH();
   return DIS_OK;

@@ -16,6 +16,9 @@ from .. import ops, lib
 from .networks import TimedModule, OutputLayerFactory, ConvParams, NormParams, LinearParams, Slots
 
 SELU, NONE = ops.ACT_SELU, ops.ACT_NONE
+# track lengths the HIP path is built for (Conv3D's kernels are instanced per track length, conv_mf has 1 x 1 kernels for 32 tl
+# input channels); the reference's dataset accepts 1..4, and tl = 1 has no second frame for the multi-frame branch
+TRACK_LENGTHS = (2, 3, 4)
 
 
 def merge_tl_bs(x):
@@ -112,7 +115,7 @@ class Conv3D(TimedModule):
 
     def __init__(self, channels_in, channels_out, neighbors=9, tl=4, ksize=3, stride=1, radius_sq=0.04):
         super().__init__(mod_name='Conv3D')
-        assert channels_in == channels_out == 32 and neighbors == 9 and tl == 4 and ksize == 3
+        assert channels_in == channels_out == 32 and neighbors == 9 and tl in TRACK_LENGTHS and ksize == 3
         self.stride = stride
         self.dense1 = Slots({0: LinearParams(3, channels_out // 2)})
         self.dense2 = Slots({0: LinearParams(channels_out // 2, channels_out)})
@@ -219,6 +222,8 @@ class FuseNet(TimedModule):
     def __init__(self, imsize, K, baseline, track_length=4, block_num=4, channels=32, max_disp=128,
                  movement_mask_en=1):
         super().__init__(mod_name='FuseNet')
+        if track_length not in TRACK_LENGTHS:
+            raise ValueError(f'FuseNet (HIP path) supports track_length in {TRACK_LENGTHS}, got {track_length!r}')
         self.movement_mask_en = movement_mask_en
         self.im_height = imsize[0]
         self.im_width = imsize[1]

@@ -507,6 +507,8 @@ int dis_mask_weight_slots(const float* wf, const float* geom, float* out, long p
 
 /* reference multi_frame_networks.py:469-512 for ALL target frames at once, in two stages.
  * geom: (tl,bs,h,w,tl,4) xyz+mask per slot; wf: (tl,bs,h,w,tl,c) gathered features (c == 32).
+ * tl: the track length, 2, 3 or 4 (the kernels are instanced per track length) in every dis_conv3d_* entry point; any other
+ * value returns DIS_ERR_UNSUPPORTED (DIS_ERR_BAD_SHAPE from dis_conv3d_csr_build, -1 from the size queries).
  *
  * stage 1, neighbour selection (reference :489-498): per output pixel the 9 candidates with the smallest masked
  * planar distance among the 3x3 x tl window (candidate id = (ky*3+kx)*tl+slot, zero-padded border).

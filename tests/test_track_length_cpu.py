@@ -1,0 +1,112 @@
+"""CPU: the step fixtures at track lengths 2 and 3 (tests/golden/*_tl{2,3}_*.npz, scripts/make_golden_track_length.py, generated
+by the imported reference with FuseNet(track_length=tl)) against the oracle, and the bit-exact Conv3D selection at 9 tl
+candidates against the reference module's own torch.topk ids."""
+import os
+import numpy as np
+import pytest
+import torch
+
+from oracle import dis_oracle as O
+from depthinspace_amd import synth
+from tests import bitexact as B
+
+TL_STEP_FIXTURES = ['mf_64_tl2_bs1', 'mf_64_tl3_bs2_rnd', 'mf_128_tl3_bs1', 'sf_64_tl2_bs1']
+TL_MF_FIXTURES = [n for n in TL_STEP_FIXTURES if n.startswith('mf_')]
+
+
+def t(x):
+    return torch.from_numpy(np.asarray(x))
+
+
+def _batch(G):
+    tl, H, W, bs = int(G['tl']), int(G['H']), int(G['W']), int(G['bs'])
+    st = synth.make_settings(H, W)
+    mk = synth.make_random_batch if int(G['random_batch']) else synth.make_batch
+    return st, mk(st, bs, tl, seed=int(G['bseed']))
+
+
+def test_fixtures_carry_their_track_length(golden_dir):
+    for name in TL_STEP_FIXTURES:
+        G = np.load(os.path.join(golden_dir, name + '.npz'))
+        tl = int(G['tl'])
+        assert f'_tl{tl}_' in name and int(G['torch_threads']) == 8, name
+        assert tuple(G['out0'].shape[:2]) == (tl, int(G['bs'])), name
+        if name.startswith('mf_'):
+            assert G['knn_idx_core'].shape[:2] == (tl, int(G['bs'])) and G['knn_idx_core'].max() < 9 * tl
+            assert G['knn_idx_quarter'].shape[:2] == (tl, int(G['bs'])) and G['knn_idx_quarter'].max() < 9 * tl
+            # the loss terms: photometric, smoothness, tl (tl - 1) / 2 geometric (+ the L1 warm-up term before epoch 2)
+            assert len(G['vals']) == 2 + tl * (tl - 1) // 2 + (1 if int(G['epoch']) < 2 else 0), name
+
+
+@pytest.mark.parametrize('name', TL_STEP_FIXTURES)
+def test_step_golden_track_length(golden_dir, name):
+    """The oracle at tl = 2 / 3 (StepContext(tl=), mf_param_shapes(tl=)) reproduces the reference's step: outputs, ordered loss
+    terms, LCN statistics and gradients, with the bars tests/test_oracle_golden.py::test_step_golden uses at tl = 4."""
+    if name.startswith('mf_') and not B.mkl_rounds_as_fixture_host():
+        pytest.skip("needs MKL kernels that round as the fixture host's (tests/golden/mkl_probe.npz)")
+    G = np.load(os.path.join(golden_dir, name + '.npz'))
+    arch, tl = str(G['arch']), int(G['tl'])
+    settings, batch = _batch(G)
+    shapes = O.mf_param_shapes(tl=tl) if arch == 'multi_frame' else O.sf_param_shapes()
+    params = O.init_params(shapes, seed=int(G['pseed']))
+    ctx = O.StepContext(settings, tl=tl)
+    res = O.train_step(ctx, arch, params, {k: t(v) for k, v in batch.items()}, adam_state={'step': 0, 'm': {}, 'v': {}},
+                       epoch=int(G['epoch']))
+    assert len(res['vals']) == len(G['vals'])
+    outs = res['out'] if isinstance(res['out'], (list, tuple)) else [res['out']]
+    for i, o in enumerate(outs):
+        assert float((o.detach() - t(G[f'out{i}'])).abs().max()) < 1e-5
+    np.testing.assert_allclose([float(v.detach()) for v in res['vals']], G['vals'], rtol=1e-5, atol=1e-7)
+    assert abs(float(res['data']['std0'].double().sum()) - float(G['std0_sum'])) < 1e-6 * abs(float(G['std0_sum']))
+    for i, k in enumerate(G['grad_keys']):
+        g = res['grads'][k]
+        if bool(G['grad_none'][i]):
+            assert g is None or float(g.abs().max()) == 0.0
+            continue
+        assert abs(float(g.double().norm()) - float(G['grad_l2'][i])) <= 1e-4 * float(G['grad_l2'][i]) + 1e-12, k
+        if 'grad:' + k in G.files:
+            ref = t(G['grad:' + k])
+            assert float((g - ref).abs().max()) <= 2e-5 * float(ref.abs().max()) + 1e-12, k
+
+
+def conv3d_select_tl(wxyz, wmask, stride, tl):
+    """tests/bitexact.py's conv3d_select for tl slots: neighbour ids (tl,bs,ho,wo,9) of all targets from the 9 tl keys"""
+    out = []
+    for ti in range(wxyz.shape[0]):
+        dist, valid = B.conv3d_keys(wxyz[ti], wmask[ti], stride, tl=tl)
+        key = np.where(valid > 0, dist, np.finfo(np.float32).max).astype(np.float32)
+        assert key.shape[-1] == 9 * tl
+        out.append(B.topk9(key.reshape(-1, key.shape[-1])).reshape(*key.shape[:-1], 9))
+    return np.stack(out, 0)
+
+
+@pytest.mark.parametrize('name', TL_MF_FIXTURES)
+def test_emulated_selection_is_the_reference_topk_at_track_length(golden_dir, name):
+    """End to end from the raw batch: the bit-exact numpy selection over 9 tl candidates (centre candidate 4 tl; nth_select.h's
+    restatement of the nth_element that torch.topk runs for k = 9 of n <= 36) == the REFERENCE module's torch.topk ids stored in
+    the fixture, every id in the same position."""
+    G = np.load(os.path.join(golden_dir, name + '.npz'))
+    tl, H, W = int(G['tl']), int(G['H']), int(G['W'])
+    st, b = _batch(G)
+    tb = {k: torch.from_numpy(v).transpose(0, 1).contiguous() if v.ndim > 2 else torch.from_numpy(v) for k, v in b.items()}
+    h, w = H // 2, W // 2
+    depth = B.disp_to_depth(tb['primary_disp'].numpy(), float(st.K[0, 0]), st.baseline)
+    depth_core = B.resize_ac(depth, h, w)
+    flow_core = {k: B.resize_flow(v[0].numpy(), h, w) for k, v in tb.items() if k.startswith('flow_')}
+    assert len(flow_core) == tl * (tl - 1)
+    wxyz, wmask = B.mf_geometry(depth_core, O.mf_core_rays(st.K, H, W).numpy(), tb['R'].numpy(), tb['t'].numpy(), flow_core)
+    assert wxyz.shape[:2] == (tl, tl)
+    assert np.array_equal(conv3d_select_tl(wxyz, wmask, 2, tl), G['knn_idx_core'])
+    hq, wq = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+    wxyz_q = B.resize_ac(wxyz, hq, wq)
+    wmask_q = (B.resize_ac(wmask, hq, wq) > 0.5).astype(np.float32)
+    assert np.array_equal(conv3d_select_tl(wxyz_q, wmask_q, 1, tl), G['knn_idx_quarter'])
+
+
+def test_oracle_parameter_shapes_follow_track_length():
+    """conv_mf is the only parameter whose shape depends on tl: a 1 x 1 conv from 32 tl channels to 32"""
+    s4, s2, s3 = O.mf_param_shapes(), O.mf_param_shapes(tl=2), O.mf_param_shapes(tl=3)
+    assert sorted(s2) == sorted(s4) == sorted(s3)
+    diff = sorted(k for k in s4 if tuple(s4[k]) != tuple(s2[k]))
+    assert diff == [f'blocks.{b}.conv_mf.1.weight' for b in range(4)]
+    assert tuple(s2[diff[0]]) == (32, 64, 1, 1) and tuple(s3[diff[0]]) == (32, 96, 1, 1)
