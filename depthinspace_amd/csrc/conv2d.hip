@@ -2330,6 +2330,69 @@ extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const 
   return DIS_OK;
 }
 
+/* The same pair in ONE launch under the three-term bf16 split (conv_bwd_fused_bf16x3.hip): operand g (in_act == 0) or g act'(q);
+ * gx (+)= its input gradient, bit-identical to dis_conv2d_fwd_bf16x3_oihw(mode 1) / dis_conv2d_dgrad_bf16x3_act; the weight gradient
+ * of x or (x_gn_stats != null, not accumulating, in_act == 0) of GroupNorm(x), as dis_conv2d_wgrad_bf16x3[_act | _gn] compute it.
+ * Workspace: dis_conv2d_bwd_fused_bf16x3_workspace(c) floats. */
+extern "C" long dis_conv2d_bwd_fused_bf16x3_workspace(int c) {
+  if (c != 32) return -1;
+  return wgrad_ws<32, 32, 3, 3, 1>();   // the per-workgroup slabs + bias partials of the weight-gradient kernels
+}
+extern "C" int dis_conv2d_bwd_fused_bf16x3(const float* g, const float* q, int in_act, const float* w_oihw, int w_o, int w_i,
+                                           int w_row_stride, float* gx, int accumulate, const float* x, const double* x_gn_stats,
+                                           const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w,
+                                           float* grad_b, float* workspace, int n, int hin, int win, int c, int grad_w_row_stride,
+                                           void* stream) {
+  if (!g || !w_oihw || !gx || !x || !grad_w || !workspace) return DIS_ERR_NULL;
+  if (n <= 0 || hin <= 0 || win <= 0) return DIS_ERR_BAD_SHAPE;
+  if (c != 32 || w_o != c || w_i != c) return DIS_ERR_UNSUPPORTED;
+  if (in_act != DIS_ACT_NONE && in_act != DIS_ACT_SELU) return DIS_ERR_UNSUPPORTED;
+  if (in_act && !q) return DIS_ERR_NULL;
+  if (x_gn_stats && (!x_gn_gamma || !x_gn_beta)) return DIS_ERR_NULL;
+  if (w_row_stride == 0) w_row_stride = w_i * 9;
+  if (w_row_stride < w_i * 9) return DIS_ERR_BAD_SHAPE;
+  if (grad_w_row_stride == 0) grad_w_row_stride = c * 9;
+  if (grad_w_row_stride < c * 9 || grad_w_row_stride % 9) return DIS_ERR_BAD_SHAPE;
+  static const bool off = getenv("DIS_BWD_FUSED") && getenv("DIS_BWD_FUSED")[0] == '0';
+  if (off || dis_f2_enabled()) return DIS_ERR_UNSUPPORTED;
+  if ((long)hin * win * c * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
+  using C = WgCfg<32, 32, 3, 3, 1>;
+  FbArgs f;
+  ConvArgs& a = f.c;
+  a.x = g; a.w = w_oihw; a.bias = nullptr; a.y = gx; a.stats = nullptr;
+  a.n = n; a.hin = hin; a.win = win; a.hv = hin; a.wv = win; a.pad_y = 1; a.pad_x = 1;
+  a.hf = hin; a.wf = win; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
+  a.act = DIS_ACT_NONE; a.accum = accumulate ? 1 : 0;
+  a.xscale = nullptr; a.yscale = nullptr;
+  a.wmode = 1; a.w_o = w_o; a.w_i = w_i; a.w_rs = w_row_stride;
+  a.xact = q;
+  a.ldx = a.ldy = c; a.cx = a.cy = c; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
+  a.gn_stats = nullptr; a.gn_gamma = nullptr; a.gn_beta = nullptr; a.gn_eps = 0.f;
+  a.ab_x = nullptr; a.ab_out = nullptr; a.ab_slots = 0; a.ab_act_y = nullptr;
+  a.gnb_coef = nullptr; a.gnb_out = nullptr; a.gnb_act = 0;
+  f.wx = x; f.wx_gn_stats = x_gn_stats; f.wx_gn_gamma = x_gn_gamma; f.wx_gn_beta = x_gn_beta; f.wx_gn_eps = x_gn_eps;
+  const int tiles_x = (win + 15) / 16, tiles_y = (hin + 7) / 8;
+  const long ntiles = (long)n * tiles_y * tiles_x;
+  long grid = num_cus();
+  if (grid > WG_WORKERS) grid = WG_WORKERS;
+  if (grid > ntiles) grid = ntiles;
+  if (grid >= 8) grid -= grid % 8;
+  if (grid < 1) grid = 1;
+  static_assert(C::PART == 9 * 32 * 32, "slab layout");
+  f.part = workspace;
+  f.bpart = grad_b ? workspace + (long)WG_WORKERS * C::PART + (long)WG_RSPLIT * C::PART : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t le = dis_fb3_launch(f, in_act, x_gn_stats != nullptr, grid, s);
+  if (le == hipErrorInvalidValue) return DIS_ERR_UNSUPPORTED;
+  if (le != hipSuccess) return (int)le;
+  const long total = (long)C::MROWS * 32;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(total, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
+                     (const float*)f.part, grad_w, C::CINB, C::NCHUNK, C::NSPLIT, C::KHB, 3, 3, 32, grad_w_row_stride / 9, C::PART,
+                     (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid);   // (cin_real = the row pitch in input channels)
+  DIS_CHECK_LAUNCH();
+  return DIS_OK;
+}
+
 // ---- wide layers as 32 x 32 channel-slice pairs (DispNetS, called from dis_convg_wgrad) ----
 // gw[g][x][tap] = sum over the pair's worker slabs; slab element [tap * 32 + xc][gc] (WxCfg<32, 32, K>: m = 16 mb + row,
 // mb = 2 tap + half).  Fixed summation order: deterministic.

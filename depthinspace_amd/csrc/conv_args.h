@@ -95,6 +95,8 @@ struct FbArgs {
   float* bpart;   // bias-gradient partials [workgroup][C], may be null
 };
 hipError_t dis_fb_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
+// conv_bwd_fused_bf16x3.hip: the same with three-term bf16 operands (plain / act / GroupNorm(x) forms; c.gnb_* and c.ab_* unused)
+hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, long grid, hipStream_t stream);
 
 // Weight prologue of the LDS-resident-weight kernels (512 threads): copy an OIHW block - w_o <= 32 rows of `row` <= 288 floats,
 // rows w_rs floats apart in memory - into LDS rows padded by one float.  ALL of a thread's loads are issued before the first

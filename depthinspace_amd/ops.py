@@ -1181,6 +1181,14 @@ def _conv_fwd_any(x, weight, cin_pad, mode, bias, y, stats, n, hin, win, cin, co
 # (profiles/r6_bwd_fused.md).  DIS_BWD_FUSED=0 keeps the two launches.
 BWD_FUSED = _os.environ.get('DIS_BWD_FUSED', '1') != '0'
 _FUSED_WS = {}
+# The forms the three-term split sends to the one-launch backward (dis_conv2d_bwd_fused_bf16x3): plain, plain_accum, act, act_accum,
+# xgn.  At the DIS-MF step's layer shapes every form measured 1 - 5 % SLOWER fused than as its two launches
+# (scripts/bwd_fused_strict_forms.py), so none is on by default; DIS_BWD_FUSED_STRICT=all (or a comma list of
+# forms) selects them.
+BWD_FUSED_STRICT_FORMS = ('plain', 'plain_accum', 'act', 'act_accum', 'xgn')
+_strict_env = _os.environ.get('DIS_BWD_FUSED_STRICT', '')
+BWD_FUSED_STRICT = frozenset(BWD_FUSED_STRICT_FORMS if _strict_env == 'all' else [f for f in _strict_env.split(',') if f])
+_FUSED3_WS = {}
 
 
 def _with_stats(ctx, y, stats):
@@ -1245,6 +1253,23 @@ def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=
                                 torch.empty(_FUSED_WS[cin], dtype=torch.float32, device=x.device), n, h, w, cin,
                                 0 if gw.is_contiguous() else gw.stride(0))
         ok, gw_ret, gb_ret = _into_sinks(weight, bias, grads, launch)
+        if ok:
+            return gpre, gw_ret, gb_ret, dgrad_done()
+    # the same under the three-term split for the forms in BWD_FUSED_STRICT (dis_conv2d_bwd_fused_bf16x3, 32 -> 32): operand gy or
+    # gy act'(y), x or GroupNorm(x); gx bit-identical to the input-gradient launch below
+    form3 = 'xgn' if xgn is not None else ('act' if act != ACT_NONE else 'plain') + ('_accum' if accumulate else '')
+    fused3 = (gx is not None and not split and BWD_FUSED and form3 in BWD_FUSED_STRICT and BF16X3 and cin == cout == cin_pad == 32 and
+              (k, pad) == (3, 1) and lz is None and (xgn is None or (act == ACT_NONE and not accumulate)))
+    if fused3 and cin not in _FUSED3_WS:
+        _FUSED3_WS[cin] = lib.fn('dis_conv2d_bwd_fused_bf16x3_workspace')(cin)
+    if fused3 and _FUSED3_WS[cin] >= 0:
+        def launch3(gw, gb):
+            assert tuple(gw.stride()[1:]) == (9, 3, 1) and gw.stride(0) % 9 == 0
+            st, gam, bet, eps = xgn if xgn is not None else (None, None, None, 0.0)
+            return lib.call_try('dis_conv2d_bwd_fused_bf16x3', g, q, in_act, weight, cout, cin, weight.stride(0), gx, acc, x, st, gam,
+                                bet, float(eps), gw, gb, torch.empty(_FUSED3_WS[cin], dtype=torch.float32, device=x.device), n, h, w,
+                                cin, 0 if gw.is_contiguous() else gw.stride(0))
+        ok, gw_ret, gb_ret = _into_sinks(weight, bias, grads, launch3)
         if ok:
             return gpre, gw_ret, gb_ret, dgrad_done()
     after = None

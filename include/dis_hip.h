@@ -425,6 +425,26 @@ int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const float* coef
                                const float* ab_act_y, double* ab_out, const float* x, const double* x_gn_stats,
                                const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b,
                                float* workspace, int n, int hin, int win, int c, int grad_w_row_stride, void* stream);
+/* Input gradient AND weight gradient of a 3x3 stride-1 pad-1 conv c -> c (c = 32) in ONE launch under the three-term bf16 split
+ * (csrc/conv_bwd_fused_bf16x3.hip): six bf16 products per MAC, fp32 accumulation.  Replaces the strict mode's pair
+ * dis_conv2d_fwd_bf16x3_oihw(mode 1) | dis_conv2d_dgrad_bf16x3_act + dis_conv2d_wgrad_bf16x3 | _act | _gn of one Conv2d node.
+ * Forms (the signature is dis_conv2d_bwd_fused_f16x2's without coef / gpre_out / ab_*):
+ *   plain: operand g (in_act == 0); gx = conv_T(g, w), or gx += it (accumulate != 0).
+ *   act:   operand g * SELU'(q) (in_act == DIS_ACT_SELU, q = the conv's activated output), formed on load; gx written or accumulated.
+ *   xgn:   x_gn_stats != NULL (with gamma, beta, eps): the weight gradient stages GroupNorm(x) as dis_conv2d_wgrad_bf16x3_gn does;
+ *          the gx side is plain, not accumulating.
+ *   gx is BIT-identical to dis_conv2d_fwd_bf16x3_oihw(mode 1) (plain) and dis_conv2d_dgrad_bf16x3_act (act) on the same operands.
+ *   weight gradient: x (n, hin, win, c) = the conv's input; grad_w (c, c, 3, 3), rows grad_w_row_stride floats apart (0 = contiguous;
+ *     a multiple of 9 >= 9 c: the slice of a wider OIHW gradient), grad_b (c) or NULL.  Per-workgroup slabs in the caller-owned
+ *     workspace of dis_conv2d_bwd_fused_bf16x3_workspace(c) floats (-1: no kernel for this channel count), reduced in a fixed order:
+ *     no float atomics, bit-reproducible.
+ * DIS_ERR_UNSUPPORTED: under the two-term split (dis_get_conv_split() == 1), with DIS_BWD_FUSED=0, and for any combination without an
+ * instance (another channel count, another activation, xgn with in_act or accumulate): the caller keeps the two launches. */
+long dis_conv2d_bwd_fused_bf16x3_workspace(int c);
+int dis_conv2d_bwd_fused_bf16x3(const float* g, const float* q, int in_act, const float* w_oihw, int w_o, int w_i, int w_row_stride,
+                                float* gx, int accumulate, const float* x, const double* x_gn_stats, const float* x_gn_gamma,
+                                const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b, float* workspace, int n,
+                                int hin, int win, int c, int grad_w_row_stride, void* stream);
 int dis_conv2d_wgrad_bf16x3_gn(const float* x, const double* gn_stats, const float* gn_gamma, const float* gn_beta,
                                float gn_eps, const float* gy, float* grad_w, float* grad_b, float* workspace, int n,
                                int hin, int win, int cin_pad, int cin_real, int cout, int k, int stride, int pad,
