@@ -11,11 +11,13 @@
 //                         "pixel on the lane" layout: lane (li,lg) owns pixel li and channels {16*mt + 4*lg + r},
 //                         which is both the MFMA B-operand layout for products that contract over channels and
 //                         the MFMA result layout, so the chain h1 -> h2 -> agg -> y needs no data movement.
-//   backward:             same mapping for the recomputed forward and the per-pixel products (d agg, d h1); the
-//                         weight gradients contract over PIXELS, so their operands are transposed once through
-//                         a small per-wave LDS tile and accumulated in MFMA accumulators across all groups of a
-//                         wave; feature gradients leave as 128-B float-atomic rows.  Parameter gradients are
-//                         reduced through per-block slabs (deterministic, no atomics).
+//   backward:             same mapping for the per-pixel products (d agg, d h1); the weight gradients contract over
+//                         PIXELS, so their operands are transposed once through a small per-wave LDS tile and
+//                         accumulated in MFMA accumulators across all groups of a wave.  conv3d_bwd2_kernel (the
+//                         package's backward) updates the feature-gradient rows class by class with plain
+//                         read-modify-writes; conv3d_bwd_kernel (round 2: float-atomic rows) is kept as the tests'
+//                         reference only.  Parameter gradients are reduced through per-block slabs (deterministic,
+//                         no atomics).
 #include "common.h"
 #include "nth_select.h"
 #include <float.h>
@@ -297,15 +299,15 @@ __device__ __forceinline__ float c3_sum16(float v) {
   return v;
 }
 
+// Backward, round 2 (dis_conv3d_knn_bwd): recomputes the forward aggregate, scatters the feature-gradient rows with float
+// atomics.  The package does not launch it: it is the reference the tests compare conv3d_bwd2_kernel against.
 template <int TL>
 __global__ __launch_bounds__(256, 2) void conv3d_bwd_kernel(const float4* __restrict__ geom,
                                                               const float* __restrict__ wf, C3Params P,
                                                               const unsigned char* __restrict__ idx,
                                                               const float* __restrict__ y, const float* __restrict__ gy,
                                                               float* __restrict__ gwf, float* __restrict__ part,
-                                                              C3Dims d, float* __restrict__ stage) {
-  // stage != nullptr: the feature-gradient rows are written to stage[(output pixel * 9 + neighbour) * 32 ..] (plain stores)
-  // instead of being scattered with float atomics; conv3d_feat_gather_kernel sums them per source row in a fixed order
+                                                              C3Dims d) {
   __shared__ C3Lds L;
   __shared__ float red[4][C3_NPARAM];
   c3_load_weights(L, P);
@@ -490,10 +492,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_bwd_kernel(const float4* __rest
       for (int j = 0; j < C3_GP / 2; ++j) {
         const int px = 2 * j + (lane >> 5), c = lane & 31;
         const long fo = F[px];
-        if (fo >= 0) {
-          if (stage) stage[((grp * C3_GP + px) * C3_NB + n) * C3_C + c] = X[px * C3_XS + c];
-          else atomicAdd(gwf + fo + c, X[px * C3_XS + c]);
-        }
+        if (fo >= 0) atomicAdd(gwf + fo + c, X[px * C3_XS + c]);
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -606,63 +605,11 @@ extern "C" int dis_conv3d_knn_fwd(const float* geom, const float* wf, const floa
 
 extern "C" long dis_conv3d_knn_bwd_workspace(void) { return (long)C3_BWD_BLOCKS * C3_NPARAM; }
 
-// grad_wf[row] (+)= sum of the staged rows of the (output pixel, neighbour) entries that selected source row `row`, in the
-// order of the CSR lists (ascending entry id: fixed, so the result is bitwise reproducible).  8 threads per row, 4 channels each.
-__global__ void conv3d_feat_gather_kernel(const float* __restrict__ stage, const int* __restrict__ offsets,
-                                          const int* __restrict__ entries, float* __restrict__ gwf, long nsrc,
-                                          int accumulate) {
-  const long total = nsrc * 8;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long d = i >> 3;
-    const int g = (int)(i & 7);
-    const int lo = offsets[d], hi = offsets[d + 1];
-    float4* out = (float4*)(gwf + d * C3_C + g * 4);
-    if (lo == hi) {
-      if (!accumulate) *out = make_float4(0.f, 0.f, 0.f, 0.f);
-      continue;
-    }
-    float4 acc = accumulate ? *out : make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int e = lo; e < hi; ++e) {
-      const float4 v = *(const float4*)(stage + (long)entries[e] * C3_C + g * 4);
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-    }
-    *out = acc;
-  }
-}
-extern "C" long dis_conv3d_knn_bwd_stage(int tl, int bs, int h, int wd, int stride) {
-  C3Dims d;
-  if (c3_dims(&d, tl, bs, h, wd, stride) != DIS_OK) return -1;
-  return (long)tl * bs * d.ho * d.wo * C3_NB * C3_C;
-}
-
-static int c3_bwd_run(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                      const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx,
-                      const float* y, const float* gy, float* grad_wf, float* gparams, float* workspace, const int* csr,
-                      float* stage, int accumulate, int tl, int bs, int h, int wd, int stride, void* stream);
 extern "C" int dis_conv3d_knn_bwd(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
                                   const float* dense2_w, const float* dense2_b, const float* w,
                                   const unsigned char* idx, const float* y, const float* gy, float* grad_wf,
                                   float* gparams, float* workspace, int tl, int bs, int h, int wd, int stride,
                                   void* stream) {
-  return c3_bwd_run(geom, wf, dense1_w, dense1_b, dense2_w, dense2_b, w, idx, y, gy, grad_wf, gparams, workspace, nullptr,
-                    nullptr, 1, tl, bs, h, wd, stride, stream);
-}
-// The same with a deterministic feature gradient: csr = dis_conv3d_csr_build(idx, ...) (layout_ops.hip), stage =
-// dis_conv3d_knn_bwd_stage() floats of scratch.  accumulate = 0: grad_wf is written (rows nobody selected get zeros: no
-// zero fill by the caller); 1: the selected rows are added to grad_wf's contents (shared gradient buffer).
-extern "C" int dis_conv3d_knn_bwd_csr(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                                      const float* dense2_w, const float* dense2_b, const float* w,
-                                      const unsigned char* idx, const float* y, const float* gy, float* grad_wf,
-                                      float* gparams, float* workspace, const int* csr, float* stage, int accumulate,
-                                      int tl, int bs, int h, int wd, int stride, void* stream) {
-  if (!csr || !stage) return DIS_ERR_NULL;
-  return c3_bwd_run(geom, wf, dense1_w, dense1_b, dense2_w, dense2_b, w, idx, y, gy, grad_wf, gparams, workspace, csr, stage,
-                    accumulate, tl, bs, h, wd, stride, stream);
-}
-static int c3_bwd_run(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                      const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx,
-                      const float* y, const float* gy, float* grad_wf, float* gparams, float* workspace, const int* csr,
-                      float* stage, int accumulate, int tl, int bs, int h, int wd, int stride, void* stream) {
   if (!geom || !wf || !dense1_w || !dense1_b || !dense2_w || !dense2_b || !w || !idx || !y || !gy || !grad_wf ||
       !gparams || !workspace)
     return DIS_ERR_NULL;
@@ -676,13 +623,8 @@ static int c3_bwd_run(const float* geom, const float* wf, const float* dense1_w,
   if (grid > C3_BWD_BLOCKS) grid = C3_BWD_BLOCKS;
   c3_with_tl(tl, [&](auto T) {
     hipLaunchKernelGGL(conv3d_bwd_kernel<decltype(T)::value>, dim3(grid), dim3(256), 0, s, (const float4*)geom, wf, P, idx, y, gy,
-                       grad_wf, workspace, d, stage);
+                       grad_wf, workspace, d);
   });
-  if (csr) {
-    const long nsrc = (long)tl * bs * h * wd * tl;
-    hipLaunchKernelGGL(conv3d_feat_gather_kernel, dim3(dis_ew_grid(nsrc * 8, 256)), dim3(256), 0, s, (const float*)stage, csr,
-                       csr + 2 * nsrc + 1, grad_wf, nsrc, accumulate);
-  }
   hipLaunchKernelGGL(c3_param_reduce_kernel, dim3(dis_cdiv(C3_NPARAM, 4)), dim3(256), 0, s, (const float*)workspace,
                      gparams, grid);
   DIS_CHECK_LAUNCH();
@@ -742,18 +684,17 @@ __device__ __forceinline__ void c3_mlp_lds(const C3Lds2& L, int li, int lg, cons
 }
 
 // ================================================================================================
-// Backward, second form (round 3; the default): conv3d_bwd2_kernel<CLS>.
+// Backward, second form (round 3; the package's backward): conv3d_bwd2_kernel.
 //   * The forward aggregate - needed for the gradient of the 32x32 mix only - is read back from the forward pass (`agg`, 128 B per
 //     output pixel) instead of being recomputed: the first neighbour loop of conv3d_bwd_kernel and its 9 feature-row gathers are
 //     gone (a third of the instructions of a kernel that is instruction-issue-bound).
 //   * The dependency chain of a group is two levels deep: {centre, selection ids} -> {neighbour geometry, feature rows,
 //     gradient rows}; the row indices go to LDS straight from the ids.
-//   * CLS = true, the DETERMINISTIC form: the 3x3 windows of output pixels whose coordinates agree modulo cn (3 at stride 1, 2 at
-//     stride 2) are disjoint, so within one such CLASS every feature-gradient row is touched by at most one (pixel, neighbour)
-//     entry.  One launch per class: the rows are accumulated with plain 16-byte read-modify-writes - no float atomics, a fifth of
-//     the scatter's instructions - and the cn*cn launches in stream order fix the summation order of every row (bitwise
-//     reproducible, no index structure to build).
-//   * CLS = false: one launch over all pixels, float-atomic scatter (cn = 1).
+//   * DETERMINISTIC: the 3x3 windows of output pixels whose coordinates agree modulo cn (3 at stride 1, 2 at stride 2) are
+//     disjoint, so within one such CLASS every feature-gradient row is touched by at most one (pixel, neighbour) entry.  One launch
+//     per class: the rows are accumulated with plain 16-byte read-modify-writes - no float atomics, a fifth of the scatter's
+//     instructions - and the cn*cn launches in stream order fix the summation order of every row (bitwise reproducible, no index
+//     structure to build).
 // Parameter gradients: per-wave accumulators over the wave's groups -> one slab per block -> fixed-order two-stage reduction.
 // (Tried and dropped: a block of 3 waves per group, 3 neighbours each, to shorten a class launch's critical path - the per-group
 //  work every wave repeats made it slower: 44 us per class launch of 1536 groups.)
@@ -792,7 +733,7 @@ union C3DShared {
   C3Lds2 L;
   float red[4][C3_NPARAM];      // (end of the kernel only: aliases the working tiles)
 };
-template <int TL, bool CLS>
+template <int TL>
 __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4* __restrict__ geom, const float* __restrict__ wf,
                                                               C3Params P, const unsigned char* __restrict__ idx,
                                                               const float* __restrict__ y, const float* __restrict__ aggp,
@@ -828,7 +769,7 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
   Q.lg = (threadIdx.x & 63) >> 4;
   __syncthreads();
   C3S(1)
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
   float* X = L.X[wave];
   float4* D = L.D[wave];
   int* R = L.R[wave];
@@ -933,8 +874,8 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
     }
     __builtin_amdgcn_wave_barrier();
     C3S(3)
-    // ---- rows of the first C3D_PD neighbours in flight: the feature rows (matrix layout) and, CLS, the gradient rows to update
-    //      (CLS: same layout - a lane updates the 16 bytes of the row it holds the gradient of; 16 rows x 64 B per instruction)
+    // ---- rows of the first C3D_PD neighbours in flight: the feature rows (matrix layout) and the gradient rows to update
+    //      (same layout - a lane updates the 16 bytes of the row it holds the gradient of; 16 rows x 64 B per instruction)
     f32x4 fvq[C3D_PD][2], preq[C3D_PD][2];
     unsigned rowq[C3D_PD];
 #define C3D_FETCH(n, q)                                                                                    \
@@ -943,10 +884,8 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
     rowq[q] = rn_ >= 0 ? (unsigned)rn_ * (C3_C * 4u) + Q.lg * 16u : BX_OOB;  /* byte offset; out of range: loads 0, store dropped */ \
     fvq[q][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wf_rs, rowq[q], 0, 0));     \
     fvq[q][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wf_rs, rowq[q], 64, 0));    \
-    if (CLS) {                                                                                             \
-      preq[q][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gwf_rs, rowq[q], 0, 0));  \
-      preq[q][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gwf_rs, rowq[q], 64, 0)); \
-    }                                                                                                      \
+    preq[q][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gwf_rs, rowq[q], 0, 0));   \
+    preq[q][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(gwf_rs, rowq[q], 64, 0));  \
   }
 #pragma unroll
     for (int n = 0; n < C3D_PD; ++n) C3D_FETCH(n, n)
@@ -1009,7 +948,6 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
       const f32x4 fv[2] = {fvq[q][0], fvq[q][1]};
       const f32x4 pre[2] = {preq[q][0], preq[q][1]};
       const unsigned rowi = rowq[q];
-      (void)pre;
       C3S(8 + 4 * n)
       if (C3D_SB) __builtin_amdgcn_sched_barrier(0);
       if (n + C3D_PD < C3_NB) C3D_FETCH(n + C3D_PD, q)
@@ -1073,23 +1011,9 @@ __global__ __launch_bounds__(256, C3D_WPE) void conv3d_bwd2_kernel(const float4*
         for (int mt = 0; mt < 2; ++mt)
           accW2[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(dpre2D[mt][r], h1D[r], accW2[mt], 0, 0, 0);
       C3S(11 + 4 * n)
-      if (CLS) {
-        // feature gradient: the lane adds its 2 x 16 bytes to the row (no other entry of this launch touches the row)
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pre[0] + dfeat[0]), gwf_rs, rowi, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pre[1] + dfeat[1]), gwf_rs, rowi, 64, 0);
-      } else {
-        // feature gradient rows: matrix layout -> row layout through LDS, 128-B rows of float atomics
-        C3_LDS_ORDER();
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) *(f32x4*)(X + Q.li * C3_XS + mt * 16 + Q.lg * 4) = dfeat[mt];
-        C3_LDS_ORDER();
-#pragma unroll
-        for (int j = 0; j < C3_GP / 2; ++j) {
-          const int px = 2 * j + (lane >> 5), c = lane & 31;
-          const int ro = R[n * C3_GP + px];
-          if (ro >= 0) atomicAdd(gwf + (long)ro * C3_C + c, X[px * C3_XS + c]);
-        }
-      }
+      // feature gradient: the lane adds its 2 x 16 bytes to the row (no other entry of this launch touches the row)
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pre[0] + dfeat[0]), gwf_rs, rowi, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, pre[1] + dfeat[1]), gwf_rs, rowi, 64, 0);
     }
     C3_LDS_ORDER();  // (the next trip's tiles)
     }
@@ -1173,10 +1097,11 @@ extern "C" long dis_conv3d_knn_bwd_det_workspace(int tl, int bs, int h, int wd, 
   const int tot = c3d_grids(d, tl, bs, stride == 1 ? 3 : 2, grids);
   return ((long)(tot > C3D_CAP ? tot : C3D_CAP) + C3D_RS) * C3_NPARAM;
 }
-static int c3_bwd2_run(bool det, const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                       const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx, const float* y,
-                       const float* agg, const float* gy, float* grad_wf, float* gparams, float* workspace, int tl, int bs, int h,
-                       int wd, int stride, void* stream) {
+extern "C" int dis_conv3d_knn_bwd_det(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
+                                      const float* dense2_w, const float* dense2_b, const float* w,
+                                      const unsigned char* idx, const float* y, const float* agg, const float* gy,
+                                      float* grad_wf, float* gparams, float* workspace, int tl, int bs, int h, int wd,
+                                      int stride, void* stream) {
   if (!geom || !wf || !dense1_w || !dense1_b || !dense2_w || !dense2_b || !w || !idx || !y || !agg || !gy || !grad_wf ||
       !gparams || !workspace)
     return DIS_ERR_NULL;
@@ -1185,51 +1110,27 @@ static int c3_bwd2_run(bool det, const float* geom, const float* wf, const float
   if (rc != DIS_OK) return rc;
   if ((long)tl * bs * h * wd * tl >= (1L << 31)) return DIS_ERR_BAD_SHAPE;  // (row indices are ints)
   // wf / grad_wf are addressed through ONE buffer descriptor each, 32-bit byte offsets, and BX_OOB (2 GiB) is the offset that
-  // drops a lane: past 2 GiB the drop offset would land INSIDE the tensor (padded candidates would load real rows and, in the
-  // class-ordered form, store into one).  Same bound as the conv launchers; the caller's alternative is dis_conv3d_knn_bwd.
+  // drops a lane: past 2 GiB the drop offset would land INSIDE the tensor (padded candidates would load real rows and store into
+  // one).  Same bound as the conv launchers.
   if ((long)tl * bs * h * wd * tl * C3_C * 4L >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   C3Params P{dense1_w, dense1_b, dense2_w, dense2_b, w};
-  int grids[9], tot;
-  if (det) {
-    const int cn = stride == 1 ? 3 : 2;
-    tot = c3d_grids(d, tl, bs, cn, grids);
-    int k = 0, base = 0;
-    for (int cy = 0; cy < cn; ++cy)
-      for (int cx = 0; cx < cn; ++cx, ++k) {
-        if (grids[k] == 0) continue;
-        c3_with_tl(tl, [&](auto T) {
-          hipLaunchKernelGGL((conv3d_bwd2_kernel<decltype(T)::value, true>), dim3(grids[k]), dim3(256), 0, s, (const float4*)geom, wf,
-                             P, idx, y, agg, gy, grad_wf, workspace + (long)base * C3_NPARAM, d, cn, cy, cx);
-        });
-        base += grids[k];
-      }
-  } else {
-    tot = c3d_grids(d, tl, bs, 1, grids);
-    c3_with_tl(tl, [&](auto T) {
-      hipLaunchKernelGGL((conv3d_bwd2_kernel<decltype(T)::value, false>), dim3(tot), dim3(256), 0, s, (const float4*)geom, wf, P, idx,
-                         y, agg, gy, grad_wf, workspace, d, 1, 0, 0);
-    });
-  }
+  const int cn = stride == 1 ? 3 : 2;
+  int grids[9];
+  const int tot = c3d_grids(d, tl, bs, cn, grids);
+  int k = 0, base = 0;
+  for (int cy = 0; cy < cn; ++cy)
+    for (int cx = 0; cx < cn; ++cx, ++k) {
+      if (grids[k] == 0) continue;
+      c3_with_tl(tl, [&](auto T) {
+        hipLaunchKernelGGL(conv3d_bwd2_kernel<decltype(T)::value>, dim3(grids[k]), dim3(256), 0, s, (const float4*)geom, wf, P,
+                           idx, y, agg, gy, grad_wf, workspace + (long)base * C3_NPARAM, d, cn, cy, cx);
+      });
+      base += grids[k];
+    }
   float* mid = workspace + (long)(tot > C3D_CAP ? tot : C3D_CAP) * C3_NPARAM;
   hipLaunchKernelGGL(c3d_reduce1_kernel, dim3(C3D_NCH, C3D_RS), dim3(256), 0, s, (const float*)workspace, mid, tot);
   hipLaunchKernelGGL(c3d_reduce2_kernel, dim3(C3D_NCH), dim3(64), 0, s, (const float*)mid, gparams);
   DIS_CHECK_LAUNCH();
   return DIS_OK;
-}
-extern "C" int dis_conv3d_knn_bwd_det(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                                      const float* dense2_w, const float* dense2_b, const float* w,
-                                      const unsigned char* idx, const float* y, const float* agg, const float* gy,
-                                      float* grad_wf, float* gparams, float* workspace, int tl, int bs, int h, int wd,
-                                      int stride, void* stream) {
-  return c3_bwd2_run(true, geom, wf, dense1_w, dense1_b, dense2_w, dense2_b, w, idx, y, agg, gy, grad_wf, gparams, workspace, tl,
-                     bs, h, wd, stride, stream);
-}
-extern "C" int dis_conv3d_knn_bwd_agg(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                                      const float* dense2_w, const float* dense2_b, const float* w,
-                                      const unsigned char* idx, const float* y, const float* agg, const float* gy,
-                                      float* grad_wf, float* gparams, float* workspace, int tl, int bs, int h, int wd,
-                                      int stride, void* stream) {
-  return c3_bwd2_run(false, geom, wf, dense1_w, dense1_b, dense2_w, dense2_b, w, idx, y, agg, gy, grad_wf, gparams, workspace, tl,
-                     bs, h, wd, stride, stream);
 }

@@ -117,7 +117,6 @@ SIGS = {
     'dis_conv3d_knn_fwd': 'ppppppppp' + 'iiiiip',
     'dis_conv3d_knn_fwd_agg': 'ppppppp' + 'ppp' + 'iiiiip',
     'dis_conv3d_knn_bwd_det': 'ppppppp' + 'ppppppp' + 'iiiiip',
-    'dis_conv3d_knn_bwd_agg': 'ppppppp' + 'ppppppp' + 'iiiiip',
     'dis_conv3d_knn_bwd_det_workspace': 'iiiii',
     'dis_geo_loss_acc_doubles': '',
     'dis_geo_loss_multi_acc_doubles': 'i',
@@ -125,10 +124,6 @@ SIGS = {
     'dis_geo_loss_bwd_multi': 'pippfppiiip',
     'dis_conv3d_knn_bwd_workspace': '',
     'dis_conv3d_knn_bwd': 'ppppppp' + 'pppppp' + 'iiiiip',
-    'dis_conv3d_knn_bwd_csr': 'ppppppp' + 'pppppp' + 'ppi' + 'iiiiip',
-    'dis_conv3d_knn_bwd_stage': 'iiiii',
-    'dis_conv3d_csr_workspace': 'iiiii',
-    'dis_conv3d_csr_build': 'ppiiiiip',
     'dis_convg_pack_workspace': 'iii',
     'dis_convg_splitk_workspace': 'iiiiiiiiiii',
     'dis_convg_run': 'ipiipppiip' + 'iiiiiiiiiiiii' + 'p',
@@ -161,7 +156,7 @@ SIGS = {
     'dis_allreduce_destroy': 'p',
 }
 _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd_fused_bf16x3_workspace', 'dis_convb_pack_desc_bytes', 'dis_convg_splitk_workspace', 'dis_convb_splitk_workspace', 'dis_conv2d_gnsums_slots', 'dis_conv2d_wgrad_workspace', 'dis_convg_pack_workspace', 'dis_convg_wgrad_workspace',
-             'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_conv3d_knn_bwd_stage', 'dis_conv3d_csr_workspace', 'dis_gather_csr_workspace',
+             'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace'}
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}

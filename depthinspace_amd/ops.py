@@ -2489,26 +2489,8 @@ def mask_weight_slots(wf, geom, join=None):
     return _MaskWeightSlots.apply(wf, geom, join)
 
 
-# DIS_CONV3D_CSR=1: Conv3D feature gradient as a fixed-order gather (bitwise reproducible) instead of the float-atomic scatter.
-# Off by default: measured on MI355X it costs 1.0 ms of the 42 ms DIS-MF step (3.04 + 0.37 ms build vs 2.41 ms; 369 vs 378
-# frames/s) - the scatter is 9 whole 128-byte rows per output pixel, which L2 atomics handle at the rate of the plain traffic
-# the staged form needs.
-CONV3D_CSR = _os.environ.get('DIS_CONV3D_CSR', '0') == '1'
-# DIS_CONV3D_BWD: which backward Conv3D runs.
-#   det (default)  class-ordered plain read-modify-write of the feature-gradient rows (dis_conv3d_knn_bwd_det): bitwise
-#                  reproducible, no index structure; the forward keeps its aggregate (128 B per output pixel) for it
-#   agg            the same kernel in one launch with the float-atomic scatter (dis_conv3d_knn_bwd_agg)
-#   atomic         round 1-2's kernel (recomputes the aggregate; float atomics), csr with DIS_CONV3D_CSR=1
-CONV3D_BWD = _os.environ.get('DIS_CONV3D_BWD', 'det')
-if CONV3D_CSR:
-    CONV3D_BWD = 'atomic'
-assert CONV3D_BWD in ('det', 'agg', 'atomic')
-
-
-def conv3d_select(geom, stride, with_csr=False):
-    """top-9 neighbour ids per output pixel (tl,bs,ho,wo,9) uint8; depends on the geometry only.
-    with_csr: also build the by-source-row index of the sets (idx.c3csr) that makes the Conv3D feature gradient a fixed-order
-    gather instead of a float-atomic scatter; shared by every layer that uses the sets."""
+def conv3d_select(geom, stride):
+    """top-9 neighbour ids per output pixel (tl,bs,ho,wo,9) uint8; depends on the geometry only."""
     geom = _c(geom)
     _chk(geom)
     tl, bs, h, wd, s, _ = geom.shape
@@ -2516,21 +2498,7 @@ def conv3d_select(geom, stride, with_csr=False):
     wo = (wd + 2 - 3) // stride + 1
     idx = torch.empty((tl, bs, ho, wo, 9), dtype=torch.uint8, device=geom.device)
     lib.call('dis_conv3d_knn_select', geom, idx, tl, bs, h, wd, stride)
-    if with_csr and CONV3D_CSR:
-        conv3d_csr(idx, h, wd, stride)
     return idx
-
-
-def conv3d_csr(idx, h, wd, stride):
-    """by-source-row CSR of the neighbour sets `idx` (tl,bs,ho,wo,9), attached to the tensor as idx.c3csr"""
-    tl, bs = idx.shape[0], idx.shape[1]
-    n = lib.fn('dis_conv3d_csr_workspace')(tl, bs, h, wd, stride)
-    if n < 0:
-        raise lib.DisHipError('conv3d csr: unsupported shape')
-    csr = torch.empty(n, dtype=torch.int32, device=idx.device)
-    lib.call('dis_conv3d_csr_build', idx, csr, tl, bs, h, wd, stride)
-    idx.c3csr = csr
-    return csr
 
 
 class _Conv3dKnn(torch.autograd.Function):
@@ -2545,13 +2513,11 @@ class _Conv3dKnn(torch.autograd.Function):
         wo = (wd + 2 - 3) // stride + 1
         assert idx.dtype == torch.uint8 and tuple(idx.shape) == (tl, bs, ho, wo, 9) and idx.is_contiguous()
         y = torch.empty((tl, bs, ho, wo, c), dtype=torch.float32, device=wf.device)
-        keep_agg = CONV3D_BWD != 'atomic' and any(ctx.needs_input_grad)
-        agg = torch.empty_like(y) if keep_agg else None
+        agg = torch.empty_like(y) if any(ctx.needs_input_grad) else None   # (the backward reads the aggregate back)
         lib.call('dis_conv3d_knn_fwd_agg', geom, wf, d1w, d1b, d2w, d2b, w, idx, y, agg, tl, bs, h, wd, stride)
         ctx.save_for_backward(geom, wf, d1w, d1b, d2w, d2b, w, idx, y, agg)
         ctx.stride = stride
         ctx.join = join
-        ctx.c3csr = getattr(idx, 'c3csr', None)
         return y
 
     @staticmethod
@@ -2561,31 +2527,12 @@ class _Conv3dKnn(torch.autograd.Function):
         join = ctx.join or _SOLE
         sunk = _sink_block((w, d1w, d1b, d2w, d2b))  # the kernel's parameter-gradient block IS the flat buffer's order
         gp = sunk if sunk is not None else torch.empty(1632, dtype=torch.float32, device=wf.device)
-        if agg is not None:
-            # class-ordered read-modify-write (det) / one launch with float atomics (agg): both ADD to the rows
-            gwf, second = join.target(wf, torch.zeros_like)
-            acc = torch.empty(lib.fn('dis_conv3d_knn_bwd_det_workspace')(tl, bs, h, wd, ctx.stride), dtype=torch.float32,
-                              device=wf.device)
-            lib.call('dis_conv3d_knn_bwd_det' if CONV3D_BWD == 'det' else 'dis_conv3d_knn_bwd_agg', geom, wf, d1w, d1b, d2w, d2b, w,
-                     idx, y, agg, _c(gy), gwf, gp, acc, tl, bs, h, wd, ctx.stride)
-            gwf = join.result(gwf, second)
-            _sinks_written()
-            if sunk is not None:
-                return (None, gwf, None, None, None, None, None, None, None, None)
-            return (None, gwf, gp[1024:1072].view(16, 3), gp[1072:1088], gp[1088:1600].view(32, 16), gp[1600:1632],
-                    gp[0:1024].view(32, 32), None, None, None)
-        acc = torch.empty(lib.fn('dis_conv3d_knn_bwd_workspace')(), dtype=torch.float32, device=wf.device)
-        if ctx.c3csr is not None:
-            # deterministic form: per-entry gradient rows staged, then summed per source row in list order
-            gwf, second = join.target(wf)
-            stage = torch.empty(lib.fn('dis_conv3d_knn_bwd_stage')(tl, bs, h, wd, ctx.stride), dtype=torch.float32,
-                                device=wf.device)
-            lib.call('dis_conv3d_knn_bwd_csr', geom, wf, d1w, d1b, d2w, d2b, w, idx, y, _c(gy), gwf, gp, acc, ctx.c3csr,
-                     stage, 1 if second else 0, tl, bs, h, wd, ctx.stride)
-        else:
-            gwf, second = join.target(wf, torch.zeros_like)  # the scatter accumulates (float atomics)
-            lib.call('dis_conv3d_knn_bwd', geom, wf, d1w, d1b, d2w, d2b, w, idx, y, _c(gy), gwf, gp, acc, tl, bs, h, wd,
-                     ctx.stride)
+        # class-ordered read-modify-write of the feature-gradient rows: ADDS to the rows
+        gwf, second = join.target(wf, torch.zeros_like)
+        acc = torch.empty(lib.fn('dis_conv3d_knn_bwd_det_workspace')(tl, bs, h, wd, ctx.stride), dtype=torch.float32,
+                          device=wf.device)
+        lib.call('dis_conv3d_knn_bwd_det', geom, wf, d1w, d1b, d2w, d2b, w, idx, y, agg, _c(gy), gwf, gp, acc, tl, bs, h, wd,
+                 ctx.stride)
         gwf = join.result(gwf, second)
         _sinks_written()
         if sunk is not None:

@@ -528,7 +528,7 @@ int dis_mask_weight_slots(const float* wf, const float* geom, float* out, long p
 /* reference multi_frame_networks.py:469-512 for ALL target frames at once, in two stages.
  * geom: (tl,bs,h,w,tl,4) xyz+mask per slot; wf: (tl,bs,h,w,tl,c) gathered features (c == 32).
  * tl: the track length, 2, 3 or 4 (the kernels are instanced per track length) in every dis_conv3d_* entry point; any other
- * value returns DIS_ERR_UNSUPPORTED (DIS_ERR_BAD_SHAPE from dis_conv3d_csr_build, -1 from the size queries).
+ * value returns DIS_ERR_UNSUPPORTED (-1 from the size queries).
  *
  * stage 1, neighbour selection (reference :489-498): per output pixel the 9 candidates with the smallest masked
  * planar distance among the 3x3 x tl window (candidate id = (ky*3+kx)*tl+slot, zero-padded border).
@@ -548,7 +548,8 @@ int dis_conv3d_knn_fwd(const float* geom, const float* wf, const float* dense1_w
 int dis_conv3d_knn_fwd_agg(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
                            const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx,
                            float* y, float* agg, int tl, int bs, int h, int wd, int stride, void* stream);
-/* gy: gradient wrt y (post-SELU).  grad_wf (zeroed) scatter-added (float atomics, 128-B rows).  gparams:
+/* Round 2's backward (recomputes agg), kept as the reference the tests hold dis_conv3d_knn_bwd_det to: the package does not
+ * call it.  gy: gradient wrt y (post-SELU).  grad_wf (zeroed) scatter-added (float atomics, 128-B rows).  gparams:
  * 32*32+16*3+16+32*16+32 floats overwritten in that order (w, dense1_w, dense1_b, dense2_w, dense2_b: the order of
  * the module's parameters()).
  * workspace: dis_conv3d_knn_bwd_workspace() floats (per-block partial slabs, summed in a fixed order). */
@@ -557,19 +558,6 @@ int dis_conv3d_knn_bwd(const float* geom, const float* wf, const float* dense1_w
                        const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx,
                        const float* y, const float* gy, float* grad_wf, float* gparams, float* workspace, int tl,
                        int bs, int h, int wd, int stride, void* stream);
-/* The same with a DETERMINISTIC feature gradient (no float atomics: bitwise reproducible).  csr = dis_conv3d_csr_build(idx):
- * the (output pixel, neighbour) entries of the neighbour sets grouped by the source row they selected, lists sorted by entry,
- * dis_conv3d_csr_workspace(...) ints, built once per geometry and shared by every Conv3D layer that uses the sets.  stage:
- * dis_conv3d_knn_bwd_stage(...) floats of scratch (the per-entry gradient rows).  accumulate = 0: grad_wf is written, rows
- * nobody selected get zeros (no zero fill by the caller); 1: the selected rows are added to grad_wf's contents. */
-long dis_conv3d_csr_workspace(int tl, int bs, int h, int w, int stride);
-int dis_conv3d_csr_build(const unsigned char* idx, int* csr, int tl, int bs, int h, int w, int stride, void* stream);
-long dis_conv3d_knn_bwd_stage(int tl, int bs, int h, int wd, int stride);
-int dis_conv3d_knn_bwd_csr(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                           const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx,
-                           const float* y, const float* gy, float* grad_wf, float* gparams, float* workspace,
-                           const int* csr, float* stage, int accumulate, int tl, int bs, int h, int wd, int stride,
-                           void* stream);
 
 /* The backward of Conv3D (reference :469-512 under autograd) with a DETERMINISTIC feature gradient and no index structure:
  * the output pixels are processed in 9 (stride 1) / 4 (stride 2) classes of pixels with pairwise disjoint 3x3 windows, one
@@ -578,12 +566,6 @@ int dis_conv3d_knn_bwd_csr(const float* geom, const float* wf, const float* dens
  * workspace: dis_conv3d_knn_bwd_det_workspace(...) floats. */
 long dis_conv3d_knn_bwd_det_workspace(int tl, int bs, int h, int wd, int stride);
 int dis_conv3d_knn_bwd_det(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
-                           const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx,
-                           const float* y, const float* agg, const float* gy, float* grad_wf, float* gparams,
-                           float* workspace, int tl, int bs, int h, int wd, int stride, void* stream);
-/* The same kernel in one launch over all pixels with the float-atomic scatter (not reproducible bit for bit); same arguments
- * and workspace. */
-int dis_conv3d_knn_bwd_agg(const float* geom, const float* wf, const float* dense1_w, const float* dense1_b,
                            const float* dense2_w, const float* dense2_b, const float* w, const unsigned char* idx,
                            const float* y, const float* agg, const float* gy, float* grad_wf, float* gparams,
                            float* workspace, int tl, int bs, int h, int wd, int stride, void* stream);

@@ -1,5 +1,5 @@
-"""Conv3D backward at the two shapes of the DIS-MF bs=4 step: float-atomic scatter vs class-ordered plain read-modify-write
-(dis_conv3d_knn_bwd_det).  Prints ms per call and the distance between the two feature / parameter gradients."""
+"""Conv3D backward at the two shapes of the DIS-MF bs=4 step: round 2's float-atomic scatter (dis_conv3d_knn_bwd, the tests'
+reference) vs class-ordered plain read-modify-write (dis_conv3d_knn_bwd_det).  Prints ms per call and the distance between the two feature / parameter gradients."""
 import os, sys, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
@@ -8,7 +8,7 @@ from depthinspace_amd import ops
 libc = ctypes.CDLL(None)
 
 
-def run(h, w, stride, reps=10, modes=('atomic', 'agg', 'det', 'det2')):
+def run(h, w, stride, reps=10, modes=('atomic', 'det', 'det2')):
     tl, bs, C = 4, 4, 32
     g = torch.Generator(device='cuda').manual_seed(1)
     yy, xx = torch.meshgrid(torch.arange(h, device='cuda', dtype=torch.float32), torch.arange(w, device='cuda', dtype=torch.float32),
@@ -46,8 +46,6 @@ def run(h, w, stride, reps=10, modes=('atomic', 'agg', 'det', 'det2')):
     def bwd(mode, gw, gp):
         if mode == 'atomic':
             ops.lib.call('dis_conv3d_knn_bwd', *args, y, gy, gw, gp, acc, tl, bs, h, w, stride)
-        elif mode == 'agg':
-            ops.lib.call('dis_conv3d_knn_bwd_agg', *args, y, agg, gy, gw, gp, accd, tl, bs, h, w, stride)
         else:
             ops.lib.call('dis_conv3d_knn_bwd_det', *args, y, agg, gy, gw, gp, accd, tl, bs, h, w, stride)
 
@@ -64,13 +62,11 @@ def run(h, w, stride, reps=10, modes=('atomic', 'agg', 'det', 'det2')):
         e1.record()
         torch.cuda.synchronize()
         print(f'h={h} w={w} stride={stride} {mode}: {e0.elapsed_time(e1) / reps:.3f} ms per call', flush=True)
-    if len(modes) < 4:
+    if len(modes) < 3:
         return
     sc = float((res['atomic'][0] - base).abs().max())
     print('   feature gradient: max |det - atomic| / scale =', float((res['det'][0] - res['atomic'][0]).abs().max()) / sc,
           ' parameters:', float((res['det'][1] - res['atomic'][1]).abs().max() / res['atomic'][1].abs().max()),
-          ' agg:', float((res['agg'][0] - res['atomic'][0]).abs().max()) / sc,
-          float((res['agg'][1] - res['atomic'][1]).abs().max() / res['atomic'][1].abs().max()),
           ' det repeats bitwise:', torch.equal(res['det'][0], res['det2'][0]) and torch.equal(res['det'][1], res['det2'][1]))
 
 

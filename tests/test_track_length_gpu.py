@@ -147,10 +147,9 @@ def test_conv3d_matches_oracle_at_track_length(tl, stride):
 
 @pytest.mark.parametrize('tl', TLS)
 @pytest.mark.parametrize('stride', [1, 2])
-def test_conv3d_backward_forms_at_track_length(tl, stride):
-    """At tl slots: the class-ordered backward (dis_conv3d_knn_bwd_det) and its one-launch float-atomic form equal the staged
-    float-atomic kernel to rounding and the class-ordered one repeats bit for bit; the CSR form (dis_conv3d_csr_build over tl slots,
-    dis_conv3d_knn_bwd_csr) matches the default in write and accumulate mode and repeats bit for bit."""
+def test_conv3d_class_ordered_backward_at_track_length(tl, stride):
+    """At tl slots: the class-ordered backward (dis_conv3d_knn_bwd_det) equals round 1-2's float-atomic kernel to rounding and
+    repeats bit for bit."""
     from depthinspace_amd import ops
     _, _, _, geom, _, g = _conv3d_inputs(tl, 70 + 10 * tl + stride)
     _, bs, h, w, _, _ = geom.shape
@@ -180,43 +179,19 @@ def test_conv3d_backward_forms_at_track_length(tl, stride):
         g_d, gp_d = base.clone(), torch.empty(1632, device='cuda')
         ops.lib.call('dis_conv3d_knn_bwd_det', *args, y, agg, gy, g_d, gp_d, accd, tl, bs, h, w, stride)
         det.append((g_d, gp_d))
-    g_a, gp_a = base.clone(), torch.empty(1632, device='cuda')
-    ops.lib.call('dis_conv3d_knn_bwd_agg', *args, y, agg, gy, g_a, gp_a, accd, tl, bs, h, w, stride)
-    for g_x, gp_x in (det[0], (g_a, gp_a)):
-        assert float((g_x - g_at).abs().max()) < 2e-6 * scale
-        assert relerr(gp_x, gp_at) < 2e-6
+    assert float((det[0][0] - g_at).abs().max()) < 2e-6 * scale
+    assert relerr(det[0][1], gp_at) < 2e-6
     assert torch.equal(det[0][0], det[1][0]) and torch.equal(det[0][1], det[1][1])   # bitwise reproducible
-    # CSR form (the staged kernel, summed per source row in a fixed order): the float-atomic scatter's result, bit-stable
-    csr = ops.conv3d_csr(idx, h, w, stride)
-    stage = torch.empty(ops.lib.fn('dis_conv3d_knn_bwd_stage')(tl, bs, h, w, stride), device='cuda')
-    outs = []
-    for rep in range(2):
-        g_acc, gp = base.clone(), torch.empty(1632, device='cuda')
-        ops.lib.call('dis_conv3d_knn_bwd_csr', *args, y, gy, g_acc, gp, acc, csr, stage, 1, tl, bs, h, w, stride)
-        g_wr = torch.full(wf.shape, float('nan'), device='cuda')   # write mode must define every row
-        ops.lib.call('dis_conv3d_knn_bwd_csr', *args, y, gy, g_wr, gp, acc, csr, stage, 0, tl, bs, h, w, stride)
-        outs.append((g_acc, g_wr, gp))
-    g_acc, g_wr, gp = outs[0]
-    assert float((g_acc - g_at).abs().max()) < 2e-6 * scale
-    assert bool(torch.isfinite(g_wr).all()) and float((g_wr - (g_at - base)).abs().max()) < 4e-6 * scale
-    assert relerr(gp, gp_at) < 1e-6
-    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    nsrc = tl * bs * h * w * tl
-    offs = csr[:nsrc + 1].cpu().numpy()
-    ents = csr[2 * nsrc + 1: 2 * nsrc + 1 + offs[-1]].cpu().numpy()
-    assert len(np.unique(ents)) == len(ents) and ents.max() < tl * bs * ho * wo * 9
 
 
 @pytest.mark.parametrize('tl', [1, 5, 8])
-def test_conv3d_entry_points_reject_other_track_lengths(tl):
+def test_conv3d_rejects_other_track_lengths(tl):
     """only the instanced track lengths are accepted: everything else is refused before a launch"""
     from depthinspace_amd import ops, lib
     geom = torch.zeros(tl, 1, 8, 8, tl, 4, device='cuda')
     idx = torch.zeros(tl, 1, 4, 4, 9, dtype=torch.uint8, device='cuda')
     assert lib.fn('dis_conv3d_knn_select')(geom.data_ptr(), idx.data_ptr(), tl, 1, 8, 8, 2, None) == -2   # DIS_ERR_UNSUPPORTED
-    assert lib.fn('dis_conv3d_knn_bwd_stage')(tl, 1, 8, 8, 2) == -1
     assert lib.fn('dis_conv3d_knn_bwd_det_workspace')(tl, 1, 8, 8, 2) == -1
-    assert lib.fn('dis_conv3d_csr_workspace')(tl, 1, 8, 8, 2) == -1
     with pytest.raises(lib.DisHipError):
         ops.conv3d_select(geom, 2)
 
