@@ -1777,7 +1777,7 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
                                                              int cinb, int nchunk, int nsplit, int khb, int kw, int kh,
                                                              int cout, int cin_real, int partsz,
                                                              const float* __restrict__ bpart, float* __restrict__ gb,
-                                                             int workers) {
+                                                             int workers, const float* __restrict__ bpart_lo = nullptr) {
   __shared__ double red[64 * WG_RW];  // (fp64 sums over the slabs: a weight gradient is a sum of ~1e5 signed per-pixel terms
                                       // at full resolution, and the slab sum is where fp32 would lose the most)
   const int mrows = khb * kw * cinb;
@@ -1831,11 +1831,13 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float* __restr
     }
   }
   // bias gradient: block b < cout/8 adds the per-workgroup bias partials of channels 8b..8b+7; thread t sums workers
-  // {t/8, t/8 + 128, ...} of channel 8b + t%8, then a fixed-order sum over the 128 sub-sums
+  // {t/8, t/8 + 128, ...} of channel 8b + t%8, then a fixed-order sum over the 128 sub-sums.  bpart_lo (conv_bwd_fused_c16.hip): the
+  // partials arrive as two floats, the second the remainder of an fp64 sum
   if (bpart && (int)blockIdx.x * 8 < cout) {
     const int co = blockIdx.x * 8 + (threadIdx.x & 7), sub = threadIdx.x >> 3;
     double s = 0.0;
-    for (int k = sub; k < workers; k += 128) s += (double)bpart[(long)k * cout + co];
+    for (int k = sub; k < workers; k += 128)
+      s += bpart_lo ? (double)bpart[(long)k * cout + co] + (double)bpart_lo[(long)k * cout + co] : (double)bpart[(long)k * cout + co];
     __syncthreads();
     red[threadIdx.x] = s;
     __syncthreads();
@@ -2326,6 +2328,86 @@ extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const 
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(total, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
                      (const float*)f.part, grad_w, C::CINB, C::NCHUNK, C::NSPLIT, C::KHB, 3, 3, 32, grad_w_row_stride / 9, C::PART,
                      (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid);   // (cin_real = the row pitch in input channels)
+  DIS_CHECK_LAUNCH();
+  return DIS_OK;
+}
+
+/* The same ONE launch for the 3x3 stride-1 pad-1 layers with 16 channels on a side (conv_bwd_fused_c16.hip): cout = w_o channels of
+ * g / q / gpre_out, cin = w_i channels of x / gx / ab_gn_x / ab_act_y.  Forms and results as above.  The kernel runs up to
+ * dis_conv2d_bwd_fused_c16_slots() workgroups (two per CU for 16 -> 16); one with channel sums runs ab_slots at most - the slots the
+ * caller allocated per sample of ab_out and hands to dis_gn_bwd_coef. */
+static long fc_max_grid(int cin, int cout) {
+  long g = (long)dis_fc_wpc(cout, cin) * num_cus();
+  return g > WG_WORKERS ? WG_WORKERS : g;
+}
+extern "C" long dis_conv2d_bwd_fused_c16_workspace(int cin, int cout) {
+  if (dis_fc_wpc(cout, cin) <= 0) return -1;
+  const long elems = 9L * cin * cout;   // (wgrad_ws's layout: slabs, the unused level-1 scratch, bias partials)
+  return (long)WG_WORKERS * elems + (long)WG_RSPLIT * elems + 2L * WG_WORKERS * cout;   // (two floats per bias partial)
+}
+extern "C" long dis_conv2d_bwd_fused_c16_slots(int cin, int cout) {
+  return dis_fc_wpc(cout, cin) <= 0 ? -1 : fc_max_grid(cin, cout);
+}
+extern "C" int dis_conv2d_bwd_fused_f16x2_c16(const float* g, const float* q, const float* coef, int in_act, float* gpre_out,
+                                              const float* w_oihw, int w_o, int w_i, int w_row_stride, float* gx, int accumulate,
+                                              const float* ab_gn_x, const float* ab_act_y, double* ab_out, int ab_slots,
+                                              const float* x, const double* x_gn_stats, const float* x_gn_gamma,
+                                              const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b, float* workspace,
+                                              int n, int hin, int win, int grad_w_row_stride, void* stream) {
+  if (!g || !w_oihw || !gx || !x || !grad_w || !workspace) return DIS_ERR_NULL;
+  if (n <= 0 || hin <= 0 || win <= 0) return DIS_ERR_BAD_SHAPE;
+  const int cout = w_o, cin = w_i;
+  if (dis_fc_wpc(cout, cin) <= 0) return DIS_ERR_UNSUPPORTED;
+  if (in_act != DIS_ACT_NONE && in_act != DIS_ACT_SELU) return DIS_ERR_UNSUPPORTED;
+  if ((coef || in_act) && !q) return DIS_ERR_NULL;
+  if (gpre_out && !coef) return DIS_ERR_BAD_SHAPE;
+  if (coef && cin != cout) return DIS_ERR_UNSUPPORTED;
+  if ((ab_out != nullptr) != (ab_gn_x != nullptr) || (ab_act_y && (!ab_out || !accumulate))) return DIS_ERR_BAD_SHAPE;
+  if (ab_out && ab_slots < 1) return DIS_ERR_BAD_SHAPE;
+  if (x_gn_stats && (!x_gn_gamma || !x_gn_beta)) return DIS_ERR_NULL;
+  if (w_row_stride == 0) w_row_stride = w_i * 9;
+  if (w_row_stride < w_i * 9) return DIS_ERR_BAD_SHAPE;
+  if (grad_w_row_stride == 0) grad_w_row_stride = cin * 9;
+  if (grad_w_row_stride < cin * 9 || grad_w_row_stride % 9) return DIS_ERR_BAD_SHAPE;
+  static const bool off = getenv("DIS_BWD_FUSED") && getenv("DIS_BWD_FUSED")[0] == '0';
+  if (off || !dis_f2_enabled()) return DIS_ERR_UNSUPPORTED;
+  const int cmax = cin > cout ? cin : cout;
+  if ((long)hin * win * cmax * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
+  FbArgs f;
+  ConvArgs& a = f.c;
+  a.x = g; a.w = w_oihw; a.bias = nullptr; a.y = gx; a.stats = nullptr;
+  a.n = n; a.hin = hin; a.win = win; a.hv = hin; a.wv = win; a.pad_y = 1; a.pad_x = 1;
+  a.hf = hin; a.wf = win; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
+  a.act = DIS_ACT_NONE; a.accum = accumulate ? 1 : 0;
+  a.xscale = nullptr; a.yscale = nullptr;
+  a.wmode = 1; a.w_o = w_o; a.w_i = w_i; a.w_rs = w_row_stride;
+  a.xact = q;
+  a.ldx = cout; a.ldy = cin; a.cx = cout; a.cy = cin; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
+  a.gn_stats = nullptr; a.gn_gamma = nullptr; a.gn_beta = nullptr; a.gn_eps = 0.f;
+  a.ab_x = ab_gn_x; a.ab_out = ab_out; a.ab_slots = ab_slots; a.ab_act_y = ab_act_y;
+  a.gnb_coef = coef; a.gnb_out = gpre_out; a.gnb_act = 0;
+  const int xsrc = (ab_gn_x && x == ab_gn_x) ? 1 : ((ab_act_y && x == ab_act_y) ? 2 : 0);
+  f.wx = x; f.wx_gn_stats = x_gn_stats; f.wx_gn_gamma = x_gn_gamma; f.wx_gn_beta = x_gn_beta; f.wx_gn_eps = x_gn_eps;
+  const int tiles_x = (win + 15) / 16, tiles_y = (hin + 15) / 16;
+  const long ntiles = (long)n * tiles_y * tiles_x;
+  long grid = fc_max_grid(cin, cout);
+  if (ab_out && grid > ab_slots) grid = ab_slots;   // (one slot of channel sums per workgroup)
+  if (grid > ntiles) grid = ntiles;
+  if (grid >= 8) grid -= grid % 8;
+  if (grid < 1) grid = 1;
+  const long elems = 9L * cin * cout;
+  f.part = workspace;
+  float* tmp = workspace + (long)WG_WORKERS * elems;
+  f.bpart = grad_b ? tmp + (long)WG_RSPLIT * elems : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t le = dis_fc_launch(f, cout, cin, in_act, x_gn_stats != nullptr, xsrc, grid, s);
+  if (le == hipErrorInvalidValue) return DIS_ERR_UNSUPPORTED;
+  if (le != hipSuccess) return (int)le;
+  // (the slab is [tap * cin + ci][cout]: one chunk of cin channels, no tap-row split; cin_real = the row pitch in input channels)
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(elems, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
+                     (const float*)f.part, grad_w, cin, 1, 1, 3, 3, 3, cout, grad_w_row_stride / 9, (int)elems,
+                     (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid,
+                     (const float*)(grad_b ? f.bpart + grid * cout : nullptr));   // (the kernel's second float of every partial)
   DIS_CHECK_LAUNCH();
   return DIS_OK;
 }

@@ -95,6 +95,10 @@ struct FbArgs {
   float* bpart;   // bias-gradient partials [workgroup][C], may be null
 };
 hipError_t dis_fb_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
+// conv_bwd_fused_c16.hip: the same for cg = gy channels, cx = x / gx channels with 16 on a side (part: slabs of 9 * cx * cg floats,
+// bpart: [workgroup][cg] sums followed by [workgroup][cg] remainders); dis_fc_wpc: workgroups per CU the kernel of the pair is built for (0: no kernel)
+hipError_t dis_fc_launch(const FbArgs& f, int cg, int cx, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
+int dis_fc_wpc(int cg, int cx);
 // conv_bwd_fused_bf16x3.hip: the same with three-term bf16 operands (plain / act / GroupNorm(x) forms; c.gnb_* and c.ab_* unused)
 hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, long grid, hipStream_t stream);
 

@@ -106,9 +106,9 @@ def _gn_coef(n, c, device):
     return torch.empty(n * (c + 2) + 4 * n * c + 2, dtype=torch.float32, device=device)
 
 
-def _gn_sums(n, c, device):
+def _gn_sums(n, c, device, slots=None):
     """-> (ab, slots): zeroed per-workgroup slots for the GroupNorm-backward channel sums an input-gradient epilogue leaves"""
-    slots = lib.fn('dis_conv2d_gnsums_slots')()
+    slots = lib.fn('dis_conv2d_gnsums_slots')() if slots is None else int(slots)
     return _zeros_d(n * slots * 2 * c, device), slots
 
 
@@ -1225,12 +1225,23 @@ def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=
         gy, lz = _gn_lazy_materialize(lz), None
     # one launch for both gradients (csrc/conv_bwd_fused.hip, 32 -> 32): it forms a token's operand (and stores it only in the
     # GroupNorm-on-load form) or takes gy (no epilogue then)
-    fused = (gx is not None and split and BWD_FUSED and BF16X3 and cin == cout == 32 and (k, pad) == (3, 1) and
-             ((not keep_gpre or xgn is not None) if lz is not None else (sums is None and xgn is None)))
-    if fused and cin not in _FUSED_WS:
-        _FUSED_WS[cin] = lib.fn('dis_conv2d_bwd_fused_workspace')(cin)
-    fused = fused and _FUSED_WS[cin] >= 0
-    ab, slots = _gn_sums(n, cin, x.device) if epi else (None, 0)
+    # (csrc/conv_bwd_fused_c16.hip: the layers with 16 channels on a side, through an entry point of their own - its workspace
+    #  function answers -1 for a pair of channel counts without a kernel; a padded input keeps the two launches.  Only a token's
+    #  forms go there: a plain gy keeps the stand-alone weight-gradient kernel, whose sums conv2d_gn_in's backward - which has no
+    #  one-launch form - reproduces BIT for bit at 16 channels (tests/test_net_ops_gpu.py holds the pair to that))
+    c16 = (cin, cout) != (32, 32)
+    fused = (gx is not None and split and BWD_FUSED and BF16X3 and cin in (16, 32) and cout in (16, 32) and cin_pad == cin and
+             (k, pad) == (3, 1) and ((not keep_gpre or xgn is not None) if lz is not None else
+                                     (sums is None and xgn is None and not c16)))
+    fkey = (cin, cout) if c16 else cin
+    if fused and fkey not in _FUSED_WS:
+        _FUSED_WS[fkey] = (lib.fn('dis_conv2d_bwd_fused_c16_workspace')(cin, cout) if c16 else
+                           lib.fn('dis_conv2d_bwd_fused_workspace')(cin))
+        if c16:
+            _FUSED_WS['slots', cin, cout] = lib.fn('dis_conv2d_bwd_fused_c16_slots')(cin, cout)
+    fused = fused and _FUSED_WS[fkey] >= 0
+    # (the 16 -> 16 kernel runs two workgroups per CU: one slot of channel sums per workgroup)
+    ab, slots = _gn_sums(n, cin, x.device, _FUSED_WS['slots', cin, cout] if fused and c16 else None) if epi else (None, 0)
     ab_x, ab_act = sums if epi else (None, None)
     acc = 1 if accumulate else 0
 
@@ -1248,13 +1259,19 @@ def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=
         def launch(gw, gb):   # (gw may be the slice of a wider OIHW gradient, conv2d_multi: the slab reduce writes it in place)
             assert tuple(gw.stride()[1:]) == (9, 3, 1) and gw.stride(0) % 9 == 0
             st, gam, bet, eps = xgn if xgn is not None else (None, None, None, 0.0)
+            ws = torch.empty(_FUSED_WS[fkey], dtype=torch.float32, device=x.device)
+            if c16:
+                return lib.call_try('dis_conv2d_bwd_fused_f16x2_c16', g, q, coef, in_act, gpre if lz is not None else None, weight,
+                                    cout, cin, weight.stride(0), gx, acc, ab_x, ab_act, ab, slots, x, st, gam, bet, float(eps), gw, gb,
+                                    ws, n, h, w, 0 if gw.is_contiguous() else gw.stride(0))
             return lib.call_try('dis_conv2d_bwd_fused_f16x2', g, q, coef, in_act, gpre if lz is not None else None, weight, cout, cin,
-                                weight.stride(0), gx, acc, ab_x, ab_act, ab, x, st, gam, bet, float(eps), gw, gb,
-                                torch.empty(_FUSED_WS[cin], dtype=torch.float32, device=x.device), n, h, w, cin,
+                                weight.stride(0), gx, acc, ab_x, ab_act, ab, x, st, gam, bet, float(eps), gw, gb, ws, n, h, w, cin,
                                 0 if gw.is_contiguous() else gw.stride(0))
         ok, gw_ret, gb_ret = _into_sinks(weight, bias, grads, launch)
         if ok:
             return gpre, gw_ret, gb_ret, dgrad_done()
+        if c16 and ab is not None:   # (no instance for this form: the two launches below take the slots of their own grid)
+            ab, slots = _gn_sums(n, cin, x.device)
     # the same under the three-term split for the forms in BWD_FUSED_STRICT (dis_conv2d_bwd_fused_bf16x3, 32 -> 32): operand gy or
     # gy act'(y), x or GroupNorm(x); gx bit-identical to the input-gradient launch below
     form3 = 'xgn' if xgn is not None else ('act' if act != ACT_NONE else 'plain') + ('_accum' if accumulate else '')

@@ -425,6 +425,21 @@ int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const float* coef
                                const float* ab_act_y, double* ab_out, const float* x, const double* x_gn_stats,
                                const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b,
                                float* workspace, int n, int hin, int win, int c, int grad_w_row_stride, void* stream);
+/* The same ONE launch for the 3x3 stride-1 pad-1 layers with 16 channels on a side (csrc/conv_bwd_fused_c16.hip): w_oihw is
+ * (w_o, w_i, 3, 3), g / q / gpre_out have w_o channels, x / gx / ab_gn_x / ab_act_y w_i.  Operand, input-gradient forms (gx BIT-identical
+ * to the two launches'), x / x_gn_*, grad_w (rows grad_w_row_stride floats apart, 0 = contiguous) and grad_b (w_o) as
+ * dis_conv2d_bwd_fused_f16x2.  The kernel runs dis_conv2d_bwd_fused_c16_slots(w_i, w_o) workgroups at most (two per CU for 16 -> 16):
+ *   workspace: dis_conv2d_bwd_fused_c16_workspace(w_i, w_o) floats (-1: no kernel for this pair of channel counts);
+ *   ab_out: (n, ab_slots, 2, w_i) doubles, ZEROED by the caller, one slot per workgroup - ab_slots is the caller's slot count (what it
+ *     hands to dis_gn_bwd_coef); a launch with channel sums runs min(ab_slots, dis_conv2d_bwd_fused_c16_slots()) workgroups.
+ * DIS_ERR_UNSUPPORTED: no instance for the combination / the three-term mode / DIS_BWD_FUSED=0 (the caller keeps the two launches). */
+long dis_conv2d_bwd_fused_c16_workspace(int cin, int cout);
+long dis_conv2d_bwd_fused_c16_slots(int cin, int cout);
+int dis_conv2d_bwd_fused_f16x2_c16(const float* g, const float* q, const float* coef, int in_act, float* gpre_out, const float* w_oihw,
+                                   int w_o, int w_i, int w_row_stride, float* gx, int accumulate, const float* ab_gn_x,
+                                   const float* ab_act_y, double* ab_out, int ab_slots, const float* x, const double* x_gn_stats,
+                                   const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b,
+                                   float* workspace, int n, int hin, int win, int grad_w_row_stride, void* stream);
 /* Input gradient AND weight gradient of a 3x3 stride-1 pad-1 conv c -> c (c = 32) in ONE launch under the three-term bf16 split
  * (csrc/conv_bwd_fused_bf16x3.hip): six bf16 products per MAC, fp32 accumulation.  Replaces the strict mode's pair
  * dis_conv2d_fwd_bf16x3_oihw(mode 1) | dis_conv2d_dgrad_bf16x3_act + dis_conv2d_wgrad_bf16x3 | _act | _gn of one Conv2d node.
