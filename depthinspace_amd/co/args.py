@@ -29,6 +29,9 @@ def get_parser():
     parser.add_argument('--architecture', help='The architecture which will be used', default='single_frame',
                         choices=['single_frame', 'multi_frame'], type=str)
     parser.add_argument('--use_pseudo_gt', help='Only applicable in single-frame model', default=False, type=str2bool)
+    # (not in the reference) backward of the geometric loss: float atomics, or order-free sums that repeat bit for bit
+    parser.add_argument('--geo_bwd', help='Backward of the geometric loss; default: the DIS_GEO_BWD environment variable, else atomic',
+                        default=None, choices=['atomic', 'det'], type=str)
     return parser
 
 

@@ -1367,6 +1367,166 @@ extern "C" int dis_geo_loss_bwd_multi(const DisGeoTerm* terms, int nterms, const
   return DIS_OK;
 }
 
+// ---- the same backward with sums that do not depend on the order of arrival (dis_geo_loss_bwd_det / _bwd_multi_det) ----
+// The addend a source pixel scatters to a tap of depth1 is -gs_k sigma w: gs_k = gscale[k] / (mask sum + 1e-8) is uniform over the
+// term, sigma = m sgn is -1, 0 or +1, and the bilinear weight w lies in [0, 1].  Pass 1 adds -sigma rint(w 2^32) to a 64-bit INTEGER
+// cell per term and destination pixel: integer addition is associative, so the cell is the same whatever order the adds arrive in,
+// and |sum w| <= the number of source pixels < 2^31 keeps it inside 63 bits.  The depth0 addend g a3[2] has one writer per pixel and
+// term: a plain store.  Pass 2 walks the terms of each distinct gradient plane in table order, sums in double, rounds to fp32 once
+// and adds to the plane with a plain read-modify-write (the atomic entry points' contract: added, the caller zero-fills).
+// A CSR index as the feature warps use would carry 4 bytes of payload behind 8 of index and cost two integer atomics per entry to
+// build; the flows are full resolution (42 M entries per step at bs 4).  Sizing: 4 taps x 8 B per source pixel = 1.36 GB of added
+// bytes per 12-term step at bs 4, 512 x 432; the launch keeps the atomic form's shape (consecutive lanes add to neighbouring cells
+// of two rows); the measured time is in profiles/geo_bwd_det.md.
+#define GEO_DET_PLANES (2 * GEO_MULTI_MAX)
+struct GeoDetPlanes {
+  float* g[GEO_DET_PLANES];           // the distinct gdepth0 / gdepth1 pointers of the table
+  unsigned short m0[GEO_DET_PLANES];  // bit k: the plane is term k's gdepth0
+  unsigned short m1[GEO_DET_PLANES];  // bit k: the plane is term k's gdepth1
+};
+__global__ __launch_bounds__(256) void geo_det_clear_kernel(unsigned long long* __restrict__ S, long count) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) S[i] = 0ull;
+}
+// pass 1: S (nterms, bs, h, w) 64-bit cells, V (nterms, bs, h, w) floats; blockIdx.y = the term.  The arithmetic up to g is
+// geo_loss_bwd_multi_kernel's.
+__global__ __launch_bounds__(256) void geo_loss_bwd_det_scatter_kernel(const GeoTermTable tab, GeoCam cam, float clampv,
+                                                                       const double* __restrict__ acc, long acc_stride,
+                                                                       const float* __restrict__ gscale,
+                                                                       unsigned long long* __restrict__ S, float* __restrict__ V,
+                                                                       int bs, int h, int w) {
+  const DisGeoTerm& q = tab.t[blockIdx.y];
+  const float* __restrict__ depth0 = q.depth0;
+  const float* __restrict__ depth1 = q.depth1;
+  const float* __restrict__ flow0 = q.flow0;
+  const float* __restrict__ mask = q.mask;
+  const long hw = (long)h * w, total = (long)bs * hw;
+  const float gs = gscale[blockIdx.y] / ((float)acc[(long)blockIdx.y * acc_stride + 1] + 1e-8f);
+  unsigned long long* __restrict__ Sk = S + (long)blockIdx.y * total;
+  float* __restrict__ Vk = V + (long)blockIdx.y * total;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const float m = mask[i];
+    float v = 0.f;
+    if (m != 0.f) {
+      const int b = (int)(i / hw);
+      const long p = i - (long)b * hw;
+      const int y = (int)(p / w), x = (int)(p - (long)y * w);
+      const float *rA = q.R0 + b * 9, *tA = q.t0 + b * 3, *rB = q.R1 + b * 9, *tB = q.t1 + b * 3;
+      float uvw[3];
+      reproject(cam, x, y, depth0[i], rA, tA, rB, tB, uvw);
+      const float d1 = uvw[2];
+      const float f0x = flow0[(long)b * 2 * hw + p], f0y = flow0[(long)b * 2 * hw + hw + p];
+      Bilin bl = bilin_zeros(f0x + (float)x, f0y + (float)y, h, w);
+      const float depth10 = bilin_fetch(depth1 + (long)b * hw, bl, w);
+      const float raw = d1 - depth10;
+      const float a = fabsf(raw);
+      if (!(clampv > 0.f && a > clampv)) {
+        const float sgn = raw > 0.f ? 1.f : (raw < 0.f ? -1.f : 0.f);
+        const float g = gs * m * sgn;
+        float ray[3], a1[3], a2[3], a3[3];
+        pixel_ray(cam.Ki, x, y, ray);
+        vec_mat(ray, rA, a1);
+        vec_matT(a1, rB, a2);
+        vec_matT(a2, cam.K, a3);
+        v = g * a3[2];
+        const long long sigma = (long long)(m * sgn);
+        if (sigma != 0) {
+          unsigned long long* s1 = Sk + (long)b * hw;
+          // (two's complement: adding the unsigned image of -sigma q is the signed add)
+          if (bl.v00) atomicAdd(s1 + (long)bl.y0 * w + bl.x0, (unsigned long long)(-sigma * __float2ll_rn(bl.nw * 4294967296.0f)));
+          if (bl.v01) atomicAdd(s1 + (long)bl.y0 * w + bl.x0 + 1, (unsigned long long)(-sigma * __float2ll_rn(bl.ne * 4294967296.0f)));
+          if (bl.v10) atomicAdd(s1 + (long)(bl.y0 + 1) * w + bl.x0, (unsigned long long)(-sigma * __float2ll_rn(bl.sw * 4294967296.0f)));
+          if (bl.v11)
+            atomicAdd(s1 + (long)(bl.y0 + 1) * w + bl.x0 + 1, (unsigned long long)(-sigma * __float2ll_rn(bl.se * 4294967296.0f)));
+        }
+      }
+    }
+    Vk[i] = v;
+  }
+}
+// pass 2: blockIdx.y = the gradient plane, one thread per pixel of it
+__global__ __launch_bounds__(256) void geo_loss_bwd_det_sum_kernel(const GeoDetPlanes pl, const double* __restrict__ acc, long acc_stride,
+                                                                   const float* __restrict__ gscale,
+                                                                   const long long* __restrict__ S, const float* __restrict__ V,
+                                                                   int nterms, long total) {
+  float* __restrict__ out = pl.g[blockIdx.y];
+  const unsigned m0 = pl.m0[blockIdx.y], m1 = pl.m1[blockIdx.y];
+  float gs[GEO_MULTI_MAX];
+#pragma unroll
+  for (int k = 0; k < GEO_MULTI_MAX; ++k)
+    gs[k] = (k < nterms && ((m1 >> k) & 1u)) ? gscale[k] / ((float)acc[(long)k * acc_stride + 1] + 1e-8f) : 0.f;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < GEO_MULTI_MAX; ++k) {
+      if (k < nterms) {
+        if ((m0 >> k) & 1u) s += (double)V[(long)k * total + i];
+        if ((m1 >> k) & 1u) s += (double)gs[k] * ((double)S[(long)k * total + i] * (1.0 / 4294967296.0));
+      }
+    }
+    out[i] += (float)s;
+  }
+}
+extern "C" long dis_geo_loss_bwd_det_workspace(int nterms, int bs, int h, int w) {
+  if (nterms <= 0 || nterms > GEO_MULTI_MAX || bs <= 0 || h <= 0 || w <= 0) return -1;
+  return (long)nterms * bs * h * w * (long)(sizeof(long long) + sizeof(float));
+}
+// tab: nterms checked terms.  acc_stride: doubles between the terms' {sum(diff mask), sum(mask)}.
+static int geo_det_run(const GeoTermTable& tab, int nterms, const float* K_host, const float* Kinv_host, float clampv, const double* acc,
+                       long acc_stride, const float* gscale, void* workspace, int bs, int h, int w, hipStream_t s) {
+  GeoDetPlanes pl = {};
+  int np = 0;
+  for (int k = 0; k < nterms; ++k)
+    for (int side = 0; side < 2; ++side) {
+      float* g = side ? tab.t[k].gdepth1 : tab.t[k].gdepth0;
+      int j = 0;
+      while (j < np && pl.g[j] != g) ++j;
+      if (j == np) pl.g[np++] = g;
+      (side ? pl.m1 : pl.m0)[j] |= (unsigned short)(1u << k);
+    }
+  GeoCam cam;
+  fill_cam(cam, K_host, Kinv_host);
+  const long total = (long)bs * h * w;
+  unsigned long long* S = (unsigned long long*)workspace;
+  float* V = (float*)(S + (long)nterms * total);
+  long gl = (total + 255) / 256;
+  if (gl > 1024) gl = 1024;
+  hipLaunchKernelGGL(geo_det_clear_kernel, dim3(dis_ew_grid((long)nterms * total, 256)), dim3(256), 0, s, S, (long)nterms * total);
+  hipLaunchKernelGGL(geo_loss_bwd_det_scatter_kernel, dim3((unsigned)gl, nterms), dim3(256), 0, s, tab, cam, clampv, acc, acc_stride,
+                     gscale, S, V, bs, h, w);
+  hipLaunchKernelGGL(geo_loss_bwd_det_sum_kernel, dim3((unsigned)gl, np), dim3(256), 0, s, pl, acc, acc_stride, gscale,
+                     (const long long*)S, (const float*)V, nterms, total);
+  DIS_CHECK_LAUNCH();
+  return DIS_OK;
+}
+extern "C" int dis_geo_loss_bwd_det(const float* depth0, const float* depth1, const float* flow0, const float* R0, const float* t0,
+                                    const float* R1, const float* t1, const float* K_host, const float* Kinv_host, float clampv,
+                                    const float* mask, const double* acc, const float* gscale, float* grad_depth0,
+                                    float* grad_depth1, int bs, int h, int w, void* workspace, void* stream) {
+  if (!depth0 || !depth1 || !flow0 || !R0 || !t0 || !R1 || !t1 || !K_host || !Kinv_host || !mask || !acc || !gscale ||
+      !grad_depth0 || !grad_depth1 || !workspace)
+    return DIS_ERR_NULL;
+  if (bs <= 0 || h <= 1 || w <= 1 || ((unsigned long long)workspace & 7ull)) return DIS_ERR_BAD_SHAPE;
+  GeoTermTable tab = {};
+  DisGeoTerm& q = tab.t[0];
+  q.depth0 = depth0; q.depth1 = depth1; q.flow0 = flow0;
+  q.R0 = R0; q.t0 = t0; q.R1 = R1; q.t1 = t1;
+  q.mask = const_cast<float*>(mask);
+  q.gdepth0 = grad_depth0; q.gdepth1 = grad_depth1;
+  return geo_det_run(tab, 1, K_host, Kinv_host, clampv, acc, 0, gscale, workspace, bs, h, w, (hipStream_t)stream);
+}
+extern "C" int dis_geo_loss_bwd_multi_det(const DisGeoTerm* terms, int nterms, const float* K_host, const float* Kinv_host, float clampv,
+                                          const double* acc, const float* gscale, int bs, int h, int w, void* workspace,
+                                          void* stream) {
+  if (!terms || !K_host || !Kinv_host || !acc || !gscale || !workspace) return DIS_ERR_NULL;
+  if (nterms <= 0 || bs <= 0 || h <= 1 || w <= 1 || ((unsigned long long)workspace & 7ull)) return DIS_ERR_BAD_SHAPE;
+  if (nterms > GEO_MULTI_MAX) return DIS_ERR_UNSUPPORTED;
+  GeoTermTable tab;
+  const int rc = geo_multi_table(terms, nterms, true, &tab);
+  if (rc != DIS_OK) return rc;
+  return geo_det_run(tab, nterms, K_host, Kinv_host, clampv, acc, 2 + 2 * GEO_MULTI_BLOCKS, gscale, workspace, bs, h, w,
+                     (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------------
 // training-time image augmentation on the device (reference data/data_manipulation.py:114-195 with the dataset's settings
 // data/dataset.py:67-70: max_shift 0 -> no affine part, max_blur 0.5, max_noise 3, max_sp_noise 5e-4), applied to the

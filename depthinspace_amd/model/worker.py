@@ -91,7 +91,8 @@ class StopWatch(object):
 
 class Worker(object):
     def __init__(self, args, seed=42, test_batch_size=4, num_workers=4, save_frequency=1, train_device=None,
-                 test_device=None, max_train_iter=-1, settings=None, output_dir=None, data_root=None, use_graph=None):
+                 test_device=None, max_train_iter=-1, settings=None, output_dir=None, data_root=None, use_graph=None,
+                 geo_bwd=None):
         self.use_pseudo_gt = args.use_pseudo_gt
         self.lcn_radius = args.lcn_radius
         self.track_length = args.track_length
@@ -116,6 +117,14 @@ class Worker(object):
         self.current_epoch = 0
         # capture the step in hipGraphs (trainer.GraphedStep) instead of ~470 eager launches per step
         self.use_graph = (os.environ.get('DIS_TRAIN_GRAPH', '0') == '1') if use_graph is None else bool(use_graph)
+        # backward of the flow-consistency loss: 'atomic' (float atomics) or 'det' (order-free sums, the same bits on every run);
+        # None: args.geo_bwd (--geo_bwd) if given, else the environment (DIS_GEO_BWD, read by ops).  The switch is ops-wide.
+        geo_bwd = getattr(args, 'geo_bwd', None) if geo_bwd is None else geo_bwd
+        if geo_bwd is not None:
+            if geo_bwd not in ('atomic', 'det'):
+                raise ValueError(f"geo_bwd must be 'atomic' or 'det', not {geo_bwd!r}")
+            from .. import ops
+            ops.set_geo_bwd_det(geo_bwd == 'det')
         self.allow_optimizer_reset = os.environ.get('DIS_ALLOW_OPTIMIZER_RESET', '0') == '1'
         # training-time augmentation (reference data/dataset.py:128-186, data_aug=True for the train set) runs on the
         # device after the host->device copy; on for tracks read from DATA_DIR, off for the in-memory synthetic scenes

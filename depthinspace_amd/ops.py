@@ -909,6 +909,22 @@ def disp_to_depth(disp, bf):
     return _DispToDepth.apply(disp, bf)
 
 
+# DIS_GEO_BWD=det: the backward of the flow-consistency loss through dis_geo_loss_bwd_det / _bwd_multi_det - integer sums per term,
+# one fp32 rounding per pixel, bit for bit the same on every call.  'atomic' (default): float atomics, equal to rounding.
+GEO_BWD_DET = {'atomic': False, 'det': True}[_os_env.environ.get('DIS_GEO_BWD', 'atomic')]
+
+
+def set_geo_bwd_det(on):
+    """select the order-free (True) or the atomic (False) backward of the flow-consistency loss; -> the previous setting"""
+    global GEO_BWD_DET
+    prev, GEO_BWD_DET = GEO_BWD_DET, bool(on)
+    return prev
+
+
+def _geo_det_workspace(nterms, bs, h, w, device):
+    return torch.empty(lib.fn('dis_geo_loss_bwd_det_workspace')(nterms, bs, h, w), dtype=torch.uint8, device=device)
+
+
 class _GeoLossDir(torch.autograd.Function):
     """One direction of the flow-consistency loss (dis_geo_loss_fwd/bwd)."""
 
@@ -943,8 +959,12 @@ class _GeoLossDir(torch.autograd.Function):
         accs = ctx.accs
         g0 = accs[0].buffer(depth0) if accs is not None else torch.zeros_like(depth0)
         g1 = accs[1].buffer(depth1) if accs is not None else torch.zeros_like(depth1)
-        lib.call('dis_geo_loss_bwd', depth0, depth1, flow0, R0, t0, R1, t1, K, Kinv, clamp, mask, acc, _c(g), g0, g1,
-                 bs, h, w)  # accumulates into g0 (+=) and g1 (atomics)
+        if GEO_BWD_DET:   # order-free sums: the same bits on every call (g0, g1 are added to, as below)
+            lib.call('dis_geo_loss_bwd_det', depth0, depth1, flow0, R0, t0, R1, t1, K, Kinv, clamp, mask, acc, _c(g), g0, g1,
+                     bs, h, w, _geo_det_workspace(1, bs, h, w, depth0.device))
+        else:
+            lib.call('dis_geo_loss_bwd', depth0, depth1, flow0, R0, t0, R1, t1, K, Kinv, clamp, mask, acc, _c(g), g0, g1,
+                     bs, h, w)  # accumulates into g0 (+=) and g1 (atomics)
         if accs is not None:
             g0, g1 = accs[0].done(), accs[1].done()
         return (g0, g1) + (None,) * 13
@@ -1019,7 +1039,11 @@ class _GeoLossAll(torch.autograd.Function):
         tl, bs, _, h, w = depth.shape
         gd = torch.zeros_like(depth)
         tab = _GeoLossAll._table(pairs, depth, R, t, mask, flows0, gdepth=gd)
-        lib.call('dis_geo_loss_bwd_multi', tab, len(pairs), K, Kinv, clamp, acc, _c(g.float()), bs, h, w)
+        if GEO_BWD_DET:
+            lib.call('dis_geo_loss_bwd_multi_det', tab, len(pairs), K, Kinv, clamp, acc, _c(g.float()), bs, h, w,
+                     _geo_det_workspace(len(pairs), bs, h, w, depth.device))
+        else:
+            lib.call('dis_geo_loss_bwd_multi', tab, len(pairs), K, Kinv, clamp, acc, _c(g.float()), bs, h, w)
         return (gd,) + (None,) * (8 + 2 * len(pairs))
 
 

@@ -155,6 +155,26 @@ int dis_geo_loss_fwd_multi(const DisGeoTerm* terms, int nterms, const float* K_h
 int dis_geo_loss_bwd_multi(const DisGeoTerm* terms, int nterms, const float* K_host, const float* Kinv_host, float clampv,
                            const double* acc, const float* gscale, int bs, int h, int w, void* stream);
 
+/* The two backward entry points above (the gradient of reference model/networks.py:564-601 / :619-655 wrt both depths; the terms of
+ * model/multi_frame_worker.py:139-158, single_frame_worker.py:126-149) with sums that do not depend on the order of arrival: the
+ * same inputs give the same bits on every call.  Per term the scattered depth1 addend -gs sigma w (gs uniform over the term, sigma =
+ * mask x sign in {-1, 0, 1}, w a bilinear weight) is accumulated as -sigma rint(w 2^32) in a 64-bit integer cell per pixel, the
+ * depth0 addend is stored; a second pass walks the terms of every distinct gradient plane in table order, adds
+ * (double)v_k + (double)gs_k ((double)S_k 2^-32), rounds to fp32 once and ADDS the result to the plane (plain read-modify-write:
+ * zeroed or pre-filled by the caller, like the atomic forms; the single-term grad_depth0 is the atomic form's bit for bit).
+ * Gradient planes are told apart by pointer: two planes are the same pointer or do not overlap.
+ * workspace: dis_geo_loss_bwd_det_workspace(nterms, bs, h, w) bytes (-1: nterms outside 1..16 or a non-positive extent; 1 term for
+ * dis_geo_loss_bwd_det), 8-byte aligned, no zeroing - the entry point clears what it sums into, on `stream`, without
+ * synchronising or allocating (capturable). */
+long dis_geo_loss_bwd_det_workspace(int nterms, int bs, int h, int w);
+int dis_geo_loss_bwd_det(const float* depth0, const float* depth1, const float* flow0, const float* R0,
+                         const float* t0, const float* R1, const float* t1, const float* K_host,
+                         const float* Kinv_host, float clamp, const float* mask, const double* acc,
+                         const float* gscale, float* grad_depth0, float* grad_depth1, int bs, int h, int w,
+                         void* workspace, void* stream);
+int dis_geo_loss_bwd_multi_det(const DisGeoTerm* terms, int nterms, const float* K_host, const float* Kinv_host, float clampv,
+                               const double* acc, const float* gscale, int bs, int h, int w, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- layout / resize / warp ---- */
 
 /* Pack up to 4 planar single-channel sources (n,1,h,w) into nhwc C=4 (NULL source => zeros).
