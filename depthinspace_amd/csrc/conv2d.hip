@@ -2332,6 +2332,44 @@ extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const 
   return DIS_OK;
 }
 
+/* Backward of the 1 x 1 multi-frame conv y = conv(x * xscale) (cin = 128 -> cout = 32) behind a GroupNorm in ONE launch
+ * (conv1x1_bwd_fused.hip): dis_conv2d_dgrad1x1_scaled_gnb + dis_conv2d_wgrad_scaled without the stored operand.  g, q (n, h, w, cout),
+ * coef (n, cout + 2) from dis_gn_bwd_coef, w_packed_dgrad the mode-1 packing of the weight; gx (n, h, w, cin) (+)= (gpre W^T) * yscale
+ * is bit-identical to dis_conv2d_dgrad1x1_scaled_gnb's; grad_w (cout, cin, 1, 1) and grad_b (cout, may be NULL) from one slab per
+ * workgroup summed in fp64 in a fixed order (no float atomics).  workspace: dis_conv2d_bwd1x1_scaled_gnb_workspace(cin, cout) floats
+ * (-1: no kernel for the shape).  DIS_MF_BWD_FUSED=0 or any other shape: DIS_ERR_UNSUPPORTED (the caller runs the two launches). */
+extern "C" long dis_conv2d_bwd1x1_scaled_gnb_workspace(int cin, int cout) {
+  if (cin != 128 || cout != 32) return -1;
+  return (long)WG_WORKERS * (128 * 32) + (long)WG_WORKERS * 32;
+}
+extern "C" int dis_conv2d_bwd1x1_scaled_gnb(const float* g, const float* q, const float* coef, int in_act, const float* w_packed_dgrad,
+                                            float* gx, const float* yscale, const float* x, const float* xscale, float* grad_w,
+                                            float* grad_b, float* workspace, int n, int h, int w, int cout, int cin, int accumulate,
+                                            void* stream) {
+  if (!g || !q || !coef || !w_packed_dgrad || !gx || !x || !grad_w || !workspace) return DIS_ERR_NULL;
+  if (n <= 0 || h <= 0 || w <= 0) return DIS_ERR_BAD_SHAPE;
+  if (cin != 128 || cout != 32 || (in_act != DIS_ACT_NONE && in_act != DIS_ACT_SELU)) return DIS_ERR_UNSUPPORTED;
+  static const bool off = getenv("DIS_MF_BWD_FUSED") && getenv("DIS_MF_BWD_FUSED")[0] == '0';
+  if (off) return DIS_ERR_UNSUPPORTED;
+  MfbArgs a;
+  a.g = g; a.q = q; a.coef = coef; a.in_act = in_act; a.w = w_packed_dgrad; a.gx = gx; a.yscale = yscale;
+  a.accum = accumulate ? 1 : 0; a.x = x; a.xscale = xscale; a.n = n; a.h = h; a.wd = w;
+  const long ntiles = (long)n * ((h + 3) / 4) * ((w + 15) / 16);
+  long grid = 2L * num_cus();   // (two workgroups per CU: 61.5 KB of LDS each)
+  if (grid > WG_WORKERS) grid = WG_WORKERS;
+  if (grid > ntiles) grid = ntiles;
+  a.part = workspace;
+  a.bpart = grad_b ? workspace + (long)WG_WORKERS * (128 * 32) : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  DIS_TAG("conv1x1_bwd_fused_kernel (fp32 MFMA)");
+  hipError_t le = dis_mfb_launch(a, grid, s);
+  if (le != hipSuccess) return (int)le;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(128L * 32, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
+                     (const float*)a.part, grad_w, 128, 1, 1, 1, 1, 1, 32, 128, 128 * 32, (const float*)a.bpart, grad_b, (int)grid);
+  DIS_CHECK_LAUNCH();
+  return DIS_OK;
+}
+
 /* The same ONE launch for the 3x3 stride-1 pad-1 layers with 16 channels on a side (conv_bwd_fused_c16.hip): cout = w_o channels of
  * g / q / gpre_out, cin = w_i channels of x / gx / ab_gn_x / ab_act_y.  Forms and results as above.  The kernel runs up to
  * dis_conv2d_bwd_fused_c16_slots() workgroups (two per CU for 16 -> 16); one with channel sums runs ab_slots at most - the slots the

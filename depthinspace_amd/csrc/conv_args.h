@@ -102,6 +102,24 @@ int dis_fc_wpc(int cg, int cx);
 // conv_bwd_fused_bf16x3.hip: the same with three-term bf16 operands (plain / act / GroupNorm(x) forms; c.gnb_* and c.ab_* unused)
 hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, long grid, hipStream_t stream);
 
+// conv1x1_bwd_fused.hip: input gradient + weight / bias gradient of the 1 x 1 multi-frame conv (128 -> 32, GroupNorm backward on load)
+struct MfbArgs {
+  const float* g;       // gradient wrt the GroupNorm's output (n, h, wd, 32)
+  const float* q;       // the GroupNorm's input = the conv's output
+  const float* coef;    // (n, 34) of dis_gn_bwd_coef
+  int in_act;
+  const float* w;       // mode-1 packing of the weight (dis_conv2d_pack_weights)
+  float* gx;            // (n, h, wd, 128)
+  const float* yscale;  // (n, h, wd, 4) multiplier of gx per 32-channel group, may be null
+  int accum;
+  const float* x;       // the conv's input (n, h, wd, 128)
+  const float* xscale;  // (n, h, wd, 4) multiplier of x, may be null
+  float* part;          // weight-gradient slabs [workgroup][128 * 32], element [ci * 32 + co]
+  float* bpart;         // bias-gradient partials [workgroup][32], may be null
+  int n, h, wd;
+};
+hipError_t dis_mfb_launch(const MfbArgs& a, long grid, hipStream_t stream);
+
 // Weight prologue of the LDS-resident-weight kernels (512 threads): copy an OIHW block - w_o <= 32 rows of `row` <= 288 floats,
 // rows w_rs floats apart in memory - into LDS rows padded by one float.  ALL of a thread's loads are issued before the first
 // is used: the plain `for (i = tid; i < n; i += 512) lds[..] = w[..]` form waits for every load in turn, 18 memory round trips

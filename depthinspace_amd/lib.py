@@ -79,6 +79,8 @@ SIGS = {
     'dis_conv2d_wgrad_split_gn': 'ppppfppppiiiiiiiiip',
     'dis_conv2d_fwd_f16x2_gnres': 'ppppfpppiiipppiiiiiip',
     'dis_conv2d_dgrad1x1_scaled_gnb': 'pppippppiiiiiip',
+    'dis_conv2d_bwd1x1_scaled_gnb_workspace': 'ii',
+    'dis_conv2d_bwd1x1_scaled_gnb': 'pppi' + 'pppppppp' + 'iiiiii' + 'p',
     'dis_conv2d_wgrad_k4s2_f16x2_gnb': 'ppppippppiiip',
     'dis_conv2d_fwd_k4s2_f16x2': 'pppppiiiip',
     'dis_conv2d_dgrad_k4s2_f16x2': 'pppiiiip',
@@ -161,7 +163,7 @@ SIGS = {
     'dis_allreduce_sum_f32': 'pplip',
     'dis_allreduce_destroy': 'p',
 }
-_RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd_fused_c16_workspace', 'dis_conv2d_bwd_fused_c16_slots', 'dis_conv2d_bwd_fused_bf16x3_workspace', 'dis_convb_pack_desc_bytes', 'dis_convg_splitk_workspace', 'dis_convb_splitk_workspace', 'dis_conv2d_gnsums_slots', 'dis_conv2d_wgrad_workspace', 'dis_convg_pack_workspace', 'dis_convg_wgrad_workspace',
+_RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_workspace', 'dis_conv2d_bwd_fused_c16_workspace', 'dis_conv2d_bwd_fused_c16_slots', 'dis_conv2d_bwd_fused_bf16x3_workspace', 'dis_convb_pack_desc_bytes', 'dis_convg_splitk_workspace', 'dis_convb_splitk_workspace', 'dis_conv2d_gnsums_slots', 'dis_conv2d_wgrad_workspace', 'dis_convg_pack_workspace', 'dis_convg_wgrad_workspace',
              'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace', 'dis_geo_loss_bwd_det_workspace'}
 

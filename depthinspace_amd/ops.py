@@ -1737,6 +1737,10 @@ def conv2d_multi(xs, weight, bias, pad=0, act=ACT_NONE, want_stats=False, gy_is_
     return out
 
 
+# DIS_MF_BWD_FUSED=0: conv_mf's backward as two launches (input gradient with the stored operand, then the weight gradient) (A/B)
+MF_BWD_FUSED = _os_env.environ.get('DIS_MF_BWD_FUSED', '1') != '0'
+
+
 class _Conv2dScaledIn(torch.autograd.Function):
     """y = conv2d(x * xscale[..., chunk]) with the multiplier applied inside the kernels: forward while the input is
     staged, input gradient in the epilogue (optionally accumulating into a GradJoin buffer), weight gradient while x
@@ -1772,9 +1776,18 @@ class _Conv2dScaledIn(torch.autograd.Function):
             gy, lz = _gn_lazy_materialize(lz), None
         gx = None
         join = ctx.join or _SOLE
+        gw, gw_ret = _sink(weight)
+        gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
         if lz is not None:
             _, lg, lq, lcoef, lin_act = lz
             gx, second = join.target(x)
+            # one launch for both gradients (csrc/conv1x1_bwd_fused.hip): the operand act'(q) (g k1 + q kx + k0) stays in LDS
+            wsz = lib.fn('dis_conv2d_bwd1x1_scaled_gnb_workspace')(cin, cout) if MF_BWD_FUSED else -1
+            if wsz >= 0 and lib.call_try('dis_conv2d_bwd1x1_scaled_gnb', lg, lq, lcoef, lin_act, _pack_w(weight, cin, 1), gx, xscale, x,
+                                         xscale, gw, gb, torch.empty(wsz, dtype=torch.float32, device=x.device), n, hin, win,
+                                         cout, cin, 1 if second else 0):
+                _sinks_written()
+                return join.result(gx, second), None, gw_ret, gb_ret, None, None, None, None, None
             gy = torch.empty_like(lg)
             lib.call('dis_conv2d_dgrad1x1_scaled_gnb', lg, lq, lcoef, lin_act, gy, _pack_w(weight, cin, 1), gx, xscale, n, hin, win,
                      cout, cin, 1 if second else 0)
@@ -1786,8 +1799,6 @@ class _Conv2dScaledIn(torch.autograd.Function):
             lib.call('dis_conv2d_fwd_scaled', gy, None, _pack_w(weight, cin, 1), None, gx, xscale, None, n, gy.shape[1],
                      gy.shape[2], cout, cin, k, 1, k - 1 - pad, ACT_NONE | (CONV_ACCUM if second else 0))
             gx = join.result(gx, second)
-        gw, gw_ret = _sink(weight)
-        gb, gb_ret = _sink(ctx.bias_ref) if has_bias else (None, None)
         wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin, cout, k, stride)
         ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
         lib.call('dis_conv2d_wgrad_scaled', x, xscale, gy, gw, gb, ws, n, hin, win, cin, cin, cout, k, stride, pad)

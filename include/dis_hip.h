@@ -310,6 +310,16 @@ long dis_conv2d_wgrad_workspace(int cin_pad, int cout, int k, int stride);
  * stride) floats.  DIS_ERR_UNSUPPORTED for any other shape. */
 int dis_conv2d_wgrad_act(const float* x, const float* gy, const float* y, int act, float* grad_w, float* grad_b, float* workspace,
                          int n, int hin, int win, int cin_pad, int cin_real, int cout, int k, int stride, int pad, void* stream);
+/* Backward of the 1 x 1 multi-frame conv y = conv(x * xscale) (cin = 128 -> cout = 32) behind a GroupNorm in ONE launch:
+ * dis_conv2d_dgrad1x1_scaled_gnb + dis_conv2d_wgrad_scaled without the stored operand gpre.  g, q (n, h, w, cout), coef from
+ * dis_gn_bwd_coef, w_packed_dgrad the mode-1 packing of the weight; gx (n, h, w, cin) (+)= (gpre W^T) * yscale, bit-identical to
+ * dis_conv2d_dgrad1x1_scaled_gnb's; grad_w (cout, cin, 1, 1), grad_b (cout) or NULL: per-workgroup slabs summed in fp64 in a fixed
+ * order (no float atomics).  yscale / xscale (n, h, w, cin / 32) may be NULL.  workspace: dis_conv2d_bwd1x1_scaled_gnb_workspace(cin,
+ * cout) floats (-1: no kernel for the shape).  DIS_ERR_UNSUPPORTED for any other shape and under DIS_MF_BWD_FUSED=0. */
+long dis_conv2d_bwd1x1_scaled_gnb_workspace(int cin, int cout);
+int dis_conv2d_bwd1x1_scaled_gnb(const float* g, const float* q, const float* coef, int in_act, const float* w_packed_dgrad,
+                                 float* gx, const float* yscale, const float* x, const float* xscale, float* grad_w, float* grad_b,
+                                 float* workspace, int n, int h, int w, int cout, int cin, int accumulate, void* stream);
 /* dis_conv2d_wgrad of conv(x * xscale) (see dis_conv2d_fwd_scaled); xscale may be NULL */
 int dis_conv2d_wgrad_scaled(const float* x, const float* xscale, const float* gy, float* grad_w, float* grad_b,
                             float* workspace, int n, int hin, int win, int cin_pad, int cin_real, int cout, int k,
