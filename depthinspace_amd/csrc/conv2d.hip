@@ -2269,19 +2269,34 @@ extern "C" long dis_conv2d_bwd_fused_workspace(int c) {
   // the weight-gradient kernels' slabs + bias partials (a pass that ends early flushes its dW accumulators into the slab)
   return wgrad_ws<32, 32, 3, 3, 1>();
 }
-extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const float* coef, int in_act, float* gpre_out,
-                                          const float* w_oihw, int w_o, int w_i, int w_row_stride, float* gx, int accumulate,
-                                          const float* ab_gn_x, const float* ab_act_y, double* ab_out, const float* x,
-                                          const double* x_gn_stats, const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps,
-                                          float* grad_w, float* grad_b, float* workspace, int n, int hin, int win, int c,
-                                          int grad_w_row_stride, void* stream) {
+
+// The one host path of the three one-launch kernels (two-term 32 -> 32 and 16 -> 16, three-term 32 -> 32).  What a family is:
+struct BwdFusedFamily {
+  int c;            // the channel count it accepts on both sides
+  int wpc;          // workgroups per CU: the grid is at most wpc x #CUs (<= 0: no kernel)
+  int tile_rows;    // rows of a tile (16 columns)
+  bool forms;       // the coef operand, the gpre store and the channel sums exist (gnb_*, ab_*); otherwise they arrive null
+  bool own_slots;   // the caller says how many slots per sample ab_out has (otherwise one per CU)
+  int bias_floats;  // floats per bias partial: 1, or 2 = an fp64 sum as float + remainder, [workgroup][c] each
+  bool f2;          // the split it belongs to: serves calls while dis_f2_enabled() reads this way
+  hipError_t (*launch)(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
+};
+// Checks (their order is the precedence of the error codes), FbArgs, grid, workspace split, launch, slab reduce.  The slab a workgroup
+// leaves is [tap * c + ci][co] (one chunk of c channels, no tap-row split: WgCfg<32, 32, 3, 3, 1>'s layout at c = 32) and the
+// workspace wgrad_ws's: WG_WORKERS slabs, the unused level-1 scratch, the bias partials.
+static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float* q, const float* coef, int in_act, float* gpre_out,
+                         const float* w_oihw, int w_o, int w_i, int w_row_stride, float* gx, int accumulate, const float* ab_gn_x,
+                         const float* ab_act_y, double* ab_out, int ab_slots, const float* x, const double* x_gn_stats,
+                         const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b,
+                         float* workspace, int n, int hin, int win, int c, int grad_w_row_stride, void* stream) {
   if (!g || !w_oihw || !gx || !x || !grad_w || !workspace) return DIS_ERR_NULL;
   if (n <= 0 || hin <= 0 || win <= 0) return DIS_ERR_BAD_SHAPE;
-  if (c != 32 || w_o != c || w_i != c) return DIS_ERR_UNSUPPORTED;
+  if (fam.wpc <= 0 || c != fam.c || w_o != c || w_i != c) return DIS_ERR_UNSUPPORTED;
   if (in_act != DIS_ACT_NONE && in_act != DIS_ACT_SELU) return DIS_ERR_UNSUPPORTED;
   if ((coef || in_act) && !q) return DIS_ERR_NULL;
   if (gpre_out && !coef) return DIS_ERR_BAD_SHAPE;
   if ((ab_out != nullptr) != (ab_gn_x != nullptr) || (ab_act_y && (!ab_out || !accumulate))) return DIS_ERR_BAD_SHAPE;
+  if (fam.own_slots && ab_out && ab_slots < 1) return DIS_ERR_BAD_SHAPE;
   if (x_gn_stats && (!x_gn_gamma || !x_gn_beta)) return DIS_ERR_NULL;
   if (w_row_stride == 0) w_row_stride = w_i * 9;
   if (w_row_stride < w_i * 9) return DIS_ERR_BAD_SHAPE;
@@ -2290,9 +2305,8 @@ extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const 
   if (grad_w_row_stride == 0) grad_w_row_stride = c * 9;
   if (grad_w_row_stride < c * 9 || grad_w_row_stride % 9) return DIS_ERR_BAD_SHAPE;
   static const bool off = getenv("DIS_BWD_FUSED") && getenv("DIS_BWD_FUSED")[0] == '0';
-  if (off || !dis_f2_enabled()) return DIS_ERR_UNSUPPORTED;
+  if (off || dis_f2_enabled() != fam.f2) return DIS_ERR_UNSUPPORTED;
   if ((long)hin * win * c * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
-  using C = WgCfg<32, 32, 3, 3, 1>;
   FbArgs f;
   ConvArgs& a = f.c;
   a.x = g; a.w = w_oihw; a.bias = nullptr; a.y = gx; a.stats = nullptr;
@@ -2304,32 +2318,48 @@ extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const 
   a.xact = q;
   a.ldx = a.ldy = c; a.cx = a.cy = c; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
   a.gn_stats = nullptr; a.gn_gamma = nullptr; a.gn_beta = nullptr; a.gn_eps = 0.f;
-  a.ab_x = ab_gn_x; a.ab_out = ab_out; a.ab_slots = num_cus(); a.ab_act_y = ab_act_y;
+  a.ab_x = ab_gn_x; a.ab_out = ab_out; a.ab_slots = !fam.forms ? 0 : (fam.own_slots ? ab_slots : num_cus()); a.ab_act_y = ab_act_y;
   a.gnb_coef = coef; a.gnb_out = gpre_out; a.gnb_act = 0;
+  // x that IS one of the epilogue's operands is fetched once
   const int xsrc = (ab_gn_x && x == ab_gn_x) ? 1 : ((ab_act_y && x == ab_act_y) ? 2 : 0);
   f.wx = x; f.wx_gn_stats = x_gn_stats; f.wx_gn_gamma = x_gn_gamma; f.wx_gn_beta = x_gn_beta; f.wx_gn_eps = x_gn_eps;
-  const int tiles_x = (win + 15) / 16, tiles_y = (hin + 15) / 16;
+  const int tiles_x = (win + 15) / 16, tiles_y = (hin + fam.tile_rows - 1) / fam.tile_rows;
   const long ntiles = (long)n * tiles_y * tiles_x;
-  long grid = num_cus();
+  long grid = (long)fam.wpc * num_cus();
   if (grid > WG_WORKERS) grid = WG_WORKERS;
+  if (fam.own_slots && ab_out && grid > ab_slots) grid = ab_slots;   // (one slot of channel sums per workgroup)
   if (grid > ntiles) grid = ntiles;
-  if (grid >= 8) grid -= grid % 8;
+  if (grid >= 8) grid -= grid % 8;   // (a multiple of 8 is dealt evenly to the XCDs: fbc_tile_share)
   if (grid < 1) grid = 1;
-  const long elems = C::PART;
-  static_assert(C::PART == 9 * 32 * 32, "slab layout");
+  const long elems = 9L * c * c;
   f.part = workspace;
-  float* tmp = workspace + (long)WG_WORKERS * elems;
-  f.bpart = grad_b ? tmp + (long)WG_RSPLIT * elems : nullptr;
+  f.bpart = grad_b ? workspace + (long)WG_WORKERS * elems + (long)WG_RSPLIT * elems : nullptr;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t le = dis_fb_launch(f, in_act, x_gn_stats != nullptr, xsrc, grid, s);
+  hipError_t le = fam.launch(f, in_act, x_gn_stats != nullptr, xsrc, grid, s);
   if (le == hipErrorInvalidValue) return DIS_ERR_UNSUPPORTED;
   if (le != hipSuccess) return (int)le;
-  const long total = (long)C::MROWS * 32;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(total, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
-                     (const float*)f.part, grad_w, C::CINB, C::NCHUNK, C::NSPLIT, C::KHB, 3, 3, 32, grad_w_row_stride / 9, C::PART,
-                     (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid);   // (cin_real = the row pitch in input channels)
+  // (cin_real = the row pitch of grad_w in input channels; the last argument: the second float of every bias partial)
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(elems, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
+                     (const float*)f.part, grad_w, c, 1, 1, 3, 3, 3, c, grad_w_row_stride / 9, (int)elems,
+                     (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid,
+                     (const float*)(grad_b && fam.bias_floats == 2 ? f.bpart + grid * c : nullptr));
   DIS_CHECK_LAUNCH();
   return DIS_OK;
+}
+static_assert(WgCfg<32, 32, 3, 3, 1>::PART == 9 * 32 * 32 && WgCfg<32, 32, 3, 3, 1>::MROWS == 9 * 32 && WgCfg<32, 32, 3, 3, 1>::CINB == 32 &&
+                  WgCfg<32, 32, 3, 3, 1>::NCHUNK == 1 && WgCfg<32, 32, 3, 3, 1>::NSPLIT == 1 && WgCfg<32, 32, 3, 3, 1>::KHB == 3,
+              "slab layout of the 32 -> 32 one-launch kernels: conv_wgrad_f16x2_kernel's");
+
+extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const float* coef, int in_act, float* gpre_out,
+                                          const float* w_oihw, int w_o, int w_i, int w_row_stride, float* gx, int accumulate,
+                                          const float* ab_gn_x, const float* ab_act_y, double* ab_out, const float* x,
+                                          const double* x_gn_stats, const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps,
+                                          float* grad_w, float* grad_b, float* workspace, int n, int hin, int win, int c,
+                                          int grad_w_row_stride, void* stream) {
+  static const BwdFusedFamily fam = {/*c*/ 32, /*wpc*/ 1, /*tile_rows*/ 16, /*forms*/ true, /*own_slots*/ false, /*bias_floats*/ 1,
+                                     /*f2*/ true, dis_fb_launch};
+  return bwd_fused_run(fam, g, q, coef, in_act, gpre_out, w_oihw, w_o, w_i, w_row_stride, gx, accumulate, ab_gn_x, ab_act_y, ab_out, 0, x,
+                       x_gn_stats, x_gn_gamma, x_gn_beta, x_gn_eps, grad_w, grad_b, workspace, n, hin, win, c, grad_w_row_stride, stream);
 }
 
 /* Backward of the 1 x 1 multi-frame conv y = conv(x * xscale) (cin = 128 -> cout = 32) behind a GroupNorm in ONE launch
@@ -2392,62 +2422,12 @@ extern "C" int dis_conv2d_bwd_fused_f16x2_c16(const float* g, const float* q, co
                                               const float* x, const double* x_gn_stats, const float* x_gn_gamma,
                                               const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b, float* workspace,
                                               int n, int hin, int win, int grad_w_row_stride, void* stream) {
-  if (!g || !w_oihw || !gx || !x || !grad_w || !workspace) return DIS_ERR_NULL;
-  if (n <= 0 || hin <= 0 || win <= 0) return DIS_ERR_BAD_SHAPE;
-  const int cout = w_o, cin = w_i;
-  if (dis_fc_wpc(cout, cin) <= 0) return DIS_ERR_UNSUPPORTED;
-  if (in_act != DIS_ACT_NONE && in_act != DIS_ACT_SELU) return DIS_ERR_UNSUPPORTED;
-  if ((coef || in_act) && !q) return DIS_ERR_NULL;
-  if (gpre_out && !coef) return DIS_ERR_BAD_SHAPE;
-  if (coef && cin != cout) return DIS_ERR_UNSUPPORTED;
-  if ((ab_out != nullptr) != (ab_gn_x != nullptr) || (ab_act_y && (!ab_out || !accumulate))) return DIS_ERR_BAD_SHAPE;
-  if (ab_out && ab_slots < 1) return DIS_ERR_BAD_SHAPE;
-  if (x_gn_stats && (!x_gn_gamma || !x_gn_beta)) return DIS_ERR_NULL;
-  if (w_row_stride == 0) w_row_stride = w_i * 9;
-  if (w_row_stride < w_i * 9) return DIS_ERR_BAD_SHAPE;
-  if (grad_w_row_stride == 0) grad_w_row_stride = cin * 9;
-  if (grad_w_row_stride < cin * 9 || grad_w_row_stride % 9) return DIS_ERR_BAD_SHAPE;
-  static const bool off = getenv("DIS_BWD_FUSED") && getenv("DIS_BWD_FUSED")[0] == '0';
-  if (off || !dis_f2_enabled()) return DIS_ERR_UNSUPPORTED;
-  const int cmax = cin > cout ? cin : cout;
-  if ((long)hin * win * cmax * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
-  FbArgs f;
-  ConvArgs& a = f.c;
-  a.x = g; a.w = w_oihw; a.bias = nullptr; a.y = gx; a.stats = nullptr;
-  a.n = n; a.hin = hin; a.win = win; a.hv = hin; a.wv = win; a.pad_y = 1; a.pad_x = 1;
-  a.hf = hin; a.wf = win; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
-  a.act = DIS_ACT_NONE; a.accum = accumulate ? 1 : 0;
-  a.xscale = nullptr; a.yscale = nullptr;
-  a.wmode = 1; a.w_o = w_o; a.w_i = w_i; a.w_rs = w_row_stride;
-  a.xact = q;
-  a.ldx = cout; a.ldy = cin; a.cx = cout; a.cy = cin; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
-  a.gn_stats = nullptr; a.gn_gamma = nullptr; a.gn_beta = nullptr; a.gn_eps = 0.f;
-  a.ab_x = ab_gn_x; a.ab_out = ab_out; a.ab_slots = ab_slots; a.ab_act_y = ab_act_y;
-  a.gnb_coef = coef; a.gnb_out = gpre_out; a.gnb_act = 0;
-  const int xsrc = (ab_gn_x && x == ab_gn_x) ? 1 : ((ab_act_y && x == ab_act_y) ? 2 : 0);
-  f.wx = x; f.wx_gn_stats = x_gn_stats; f.wx_gn_gamma = x_gn_gamma; f.wx_gn_beta = x_gn_beta; f.wx_gn_eps = x_gn_eps;
-  const int tiles_x = (win + 15) / 16, tiles_y = (hin + 15) / 16;
-  const long ntiles = (long)n * tiles_y * tiles_x;
-  long grid = fc_max_grid(cin, cout);
-  if (ab_out && grid > ab_slots) grid = ab_slots;   // (one slot of channel sums per workgroup)
-  if (grid > ntiles) grid = ntiles;
-  if (grid >= 8) grid -= grid % 8;
-  if (grid < 1) grid = 1;
-  const long elems = 9L * cin * cout;
-  f.part = workspace;
-  float* tmp = workspace + (long)WG_WORKERS * elems;
-  f.bpart = grad_b ? tmp + (long)WG_RSPLIT * elems : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t le = dis_fc_launch(f, cout, cin, in_act, x_gn_stats != nullptr, xsrc, grid, s);
-  if (le == hipErrorInvalidValue) return DIS_ERR_UNSUPPORTED;
-  if (le != hipSuccess) return (int)le;
-  // (the slab is [tap * cin + ci][cout]: one chunk of cin channels, no tap-row split; cin_real = the row pitch in input channels)
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(elems, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
-                     (const float*)f.part, grad_w, cin, 1, 1, 3, 3, 3, cout, grad_w_row_stride / 9, (int)elems,
-                     (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid,
-                     (const float*)(grad_b ? f.bpart + grid * cout : nullptr));   // (the kernel's second float of every partial)
-  DIS_CHECK_LAUNCH();
-  return DIS_OK;
+  // (a pair without a kernel - dis_fc_wpc 0 - is DIS_ERR_UNSUPPORTED; the kernel keeps fp64 bias sums: two floats per partial)
+  const BwdFusedFamily fam = {/*c*/ 16, /*wpc*/ dis_fc_wpc(w_o, w_i), /*tile_rows*/ 16, /*forms*/ true, /*own_slots*/ true,
+                              /*bias_floats*/ 2, /*f2*/ true, dis_fc_launch};
+  return bwd_fused_run(fam, g, q, coef, in_act, gpre_out, w_oihw, w_o, w_i, w_row_stride, gx, accumulate, ab_gn_x, ab_act_y, ab_out,
+                       ab_slots, x, x_gn_stats, x_gn_gamma, x_gn_beta, x_gn_eps, grad_w, grad_b, workspace, n, hin, win, fam.c,
+                       grad_w_row_stride, stream);
 }
 
 /* The same pair in ONE launch under the three-term bf16 split (conv_bwd_fused_bf16x3.hip): operand g (in_act == 0) or g act'(q);
@@ -2463,54 +2443,10 @@ extern "C" int dis_conv2d_bwd_fused_bf16x3(const float* g, const float* q, int i
                                            const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w,
                                            float* grad_b, float* workspace, int n, int hin, int win, int c, int grad_w_row_stride,
                                            void* stream) {
-  if (!g || !w_oihw || !gx || !x || !grad_w || !workspace) return DIS_ERR_NULL;
-  if (n <= 0 || hin <= 0 || win <= 0) return DIS_ERR_BAD_SHAPE;
-  if (c != 32 || w_o != c || w_i != c) return DIS_ERR_UNSUPPORTED;
-  if (in_act != DIS_ACT_NONE && in_act != DIS_ACT_SELU) return DIS_ERR_UNSUPPORTED;
-  if (in_act && !q) return DIS_ERR_NULL;
-  if (x_gn_stats && (!x_gn_gamma || !x_gn_beta)) return DIS_ERR_NULL;
-  if (w_row_stride == 0) w_row_stride = w_i * 9;
-  if (w_row_stride < w_i * 9) return DIS_ERR_BAD_SHAPE;
-  if (grad_w_row_stride == 0) grad_w_row_stride = c * 9;
-  if (grad_w_row_stride < c * 9 || grad_w_row_stride % 9) return DIS_ERR_BAD_SHAPE;
-  static const bool off = getenv("DIS_BWD_FUSED") && getenv("DIS_BWD_FUSED")[0] == '0';
-  if (off || dis_f2_enabled()) return DIS_ERR_UNSUPPORTED;
-  if ((long)hin * win * c * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
-  using C = WgCfg<32, 32, 3, 3, 1>;
-  FbArgs f;
-  ConvArgs& a = f.c;
-  a.x = g; a.w = w_oihw; a.bias = nullptr; a.y = gx; a.stats = nullptr;
-  a.n = n; a.hin = hin; a.win = win; a.hv = hin; a.wv = win; a.pad_y = 1; a.pad_x = 1;
-  a.hf = hin; a.wf = win; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
-  a.act = DIS_ACT_NONE; a.accum = accumulate ? 1 : 0;
-  a.xscale = nullptr; a.yscale = nullptr;
-  a.wmode = 1; a.w_o = w_o; a.w_i = w_i; a.w_rs = w_row_stride;
-  a.xact = q;
-  a.ldx = a.ldy = c; a.cx = a.cy = c; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
-  a.gn_stats = nullptr; a.gn_gamma = nullptr; a.gn_beta = nullptr; a.gn_eps = 0.f;
-  a.ab_x = nullptr; a.ab_out = nullptr; a.ab_slots = 0; a.ab_act_y = nullptr;
-  a.gnb_coef = nullptr; a.gnb_out = nullptr; a.gnb_act = 0;
-  f.wx = x; f.wx_gn_stats = x_gn_stats; f.wx_gn_gamma = x_gn_gamma; f.wx_gn_beta = x_gn_beta; f.wx_gn_eps = x_gn_eps;
-  const int tiles_x = (win + 15) / 16, tiles_y = (hin + 7) / 8;
-  const long ntiles = (long)n * tiles_y * tiles_x;
-  long grid = num_cus();
-  if (grid > WG_WORKERS) grid = WG_WORKERS;
-  if (grid > ntiles) grid = ntiles;
-  if (grid >= 8) grid -= grid % 8;
-  if (grid < 1) grid = 1;
-  static_assert(C::PART == 9 * 32 * 32, "slab layout");
-  f.part = workspace;
-  f.bpart = grad_b ? workspace + (long)WG_WORKERS * C::PART + (long)WG_RSPLIT * C::PART : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t le = dis_fb3_launch(f, in_act, x_gn_stats != nullptr, grid, s);
-  if (le == hipErrorInvalidValue) return DIS_ERR_UNSUPPORTED;
-  if (le != hipSuccess) return (int)le;
-  const long total = (long)C::MROWS * 32;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(total, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
-                     (const float*)f.part, grad_w, C::CINB, C::NCHUNK, C::NSPLIT, C::KHB, 3, 3, 32, grad_w_row_stride / 9, C::PART,
-                     (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid);   // (cin_real = the row pitch in input channels)
-  DIS_CHECK_LAUNCH();
-  return DIS_OK;
+  static const BwdFusedFamily fam = {/*c*/ 32, /*wpc*/ 1, /*tile_rows*/ 8, /*forms*/ false, /*own_slots*/ false, /*bias_floats*/ 1,
+                                     /*f2*/ false, dis_fb3_launch};
+  return bwd_fused_run(fam, g, q, nullptr, in_act, nullptr, w_oihw, w_o, w_i, w_row_stride, gx, accumulate, nullptr, nullptr, nullptr, 0, x,
+                       x_gn_stats, x_gn_gamma, x_gn_beta, x_gn_eps, grad_w, grad_b, workspace, n, hin, win, c, grad_w_row_stride, stream);
 }
 
 // ---- wide layers as 32 x 32 channel-slice pairs (DispNetS, called from dis_convg_wgrad) ----

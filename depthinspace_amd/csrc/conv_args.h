@@ -1,4 +1,6 @@
-// Argument blocks of the convolution kernels (shared by conv2d.hip and conv_f16x2.hip).
+// Argument blocks of the convolution kernels and the declarations of their launchers: shared by conv2d.hip (the entry points) and the
+// kernel files (conv_f16x2.hip, conv_gen.hip, conv_k4s2.hip, conv1x1_bwd_fused.hip and the three one-launch 3x3 backward files
+// conv_bwd_fused*.hip, whose common parts are in conv_bwd_fused_common.h).
 #pragma once
 #include "common.h"
 
@@ -94,13 +96,16 @@ struct FbArgs {
   float* part;    // weight-gradient slabs [workgroup][9 * C * C], element [(tap * C + ci) * C + co] (conv_wgrad_f16x2_kernel's layout)
   float* bpart;   // bias-gradient partials [workgroup][C], may be null
 };
+// The launchers of the three one-launch files share one signature (conv2d.hip's bwd_fused_run calls them through a table); their
+// shared device helpers, form table and launch helper are in conv_bwd_fused_common.h.  hipErrorInvalidValue: no instance for the form.
 hipError_t dis_fb_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
-// conv_bwd_fused_c16.hip: the same for cg = gy channels, cx = x / gx channels with 16 on a side (part: slabs of 9 * cx * cg floats,
-// bpart: [workgroup][cg] sums followed by [workgroup][cg] remainders); dis_fc_wpc: workgroups per CU the kernel of the pair is built for (0: no kernel)
-hipError_t dis_fc_launch(const FbArgs& f, int cg, int cx, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
+// conv_bwd_fused_c16.hip: the same for 16 -> 16 (c.cx = channels of gy, c.cy = channels of x / gx; part: slabs of 9 * 16 * 16 floats,
+// bpart: [workgroup][16] sums followed by [workgroup][16] remainders); dis_fc_wpc: workgroups per CU the kernel of the pair is built
+// for (0: no kernel)
+hipError_t dis_fc_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
 int dis_fc_wpc(int cg, int cx);
-// conv_bwd_fused_bf16x3.hip: the same with three-term bf16 operands (plain / act / GroupNorm(x) forms; c.gnb_* and c.ab_* unused)
-hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, long grid, hipStream_t stream);
+// conv_bwd_fused_bf16x3.hip: the same with three-term bf16 operands (plain / act / GroupNorm(x) forms; c.gnb_* and c.ab_* unused, xsrc 0)
+hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
 
 // conv1x1_bwd_fused.hip: input gradient + weight / bias gradient of the 1 x 1 multi-frame conv (128 -> 32, GroupNorm backward on load)
 struct MfbArgs {

@@ -26,7 +26,7 @@
 // No cross-wave reduction of dW at all: a wave's 9 tiles are its own elements of the workgroup's slab, written once per workgroup and
 // summed over workgroups by wgrad_reduce_kernel (fixed order, fp64).
 // dW scales: the gy halo carries the input gradient's per-tile scale 2^sg(t); x is split with 2^(S - sg(t)), S a WORKGROUP-uniform
-// exponent set by the first tile that has something to add (FB_SMARGIN bits of headroom), so that every term of the sum carries 2^S.
+// exponent set by the first tile that has something to add (FBC_SMARGIN bits of headroom), so that every term of the sum carries 2^S.
 // A later tile whose product magnitude exceeds the headroom makes the workgroup LEAVE the tile loop (inside it only matrix instructions
 // touch the dW accumulators - a rescale branch in the loop makes the allocator keep them in vector registers): the accumulators go to
 // the slab (scaled by 2^-S, added to what an earlier pass left there), a new pass starts from zero with a new S at the same tile.
@@ -36,35 +36,8 @@
 // launches in every form behind a GroupNorm: 530 - 600 registers of state against 512.  The tile split above needs 110 - 256 + 256 and
 // is 0.79 - 0.95 of the two launches (same-box A/B per form); the step uses it wherever an instance exists (DIS_BWD_FUSED=0: off).
 // LDS: weights 36.9 KB + halo 51.8 KB + x tile 41.0 KB + 1.2 KB = 130.9 KB.
-#include "conv_args.h"
-#include <type_traits>
+#include "conv_bwd_fused_common.h"
 
-
-typedef short fb_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x8 fb_tr_read8(const unsigned short* p0, const unsigned short* p1) {
-  const fb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fb_s16x4*)p0);
-  const fb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fb_s16x4*)p1);
-  return (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-// the tap / channel -> k-slot map of conv_f16x2.hip's f2_weight for 32 channels, input-gradient order (flipped taps, transposed)
-__device__ __forceinline__ float fb_weight(const float* w, int stride_row, int wo, int wi, int ks, int lg, int j, int co) {
-  const int c = 8 * lg + j;
-  return (c < wo && co < wi) ? w[c * stride_row + co * 9 + (8 - ks)] : 0.f;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void fb_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    fb_static_for<I + 1, N>(f);
-  }
-}
-
-#ifndef FB_ZLIT
-#define FB_ZLIT 1   // the first product of an input-gradient accumulator starts from a zero literal (no register moves)
-#endif
-#ifndef FB_BLIND
-#define FB_BLIND 0   // (re-blinding p0 with an empty asm statement produced WRONG results in the INACT instances: off)
-#endif
 // Diagnostic build only (scripts/diag/fb_stamps.py, -DFB_STAMP): per-wave s_memtime sums of the phases of a tile
 #ifdef FB_STAMP
 __device__ unsigned long long fb_stamps[256 * 4 * 12];
@@ -82,9 +55,6 @@ extern "C" int dis_debug_fb_stamps(unsigned long long* host) { return (int)hipMe
 #define FB_TC 16
 #ifndef FB_XGRP
 #define FB_XGRP 2   // x pieces staged together, stage by stage (independent chains: one wave per SIMD exposes every dependent latency)
-#endif
-#ifndef FB_SMARGIN
-#define FB_SMARGIN 6   // bits of headroom the dW exponent keeps when it is (re)set: a later tile may be 2^6 larger before the accumulators move again
 #endif
 struct FbCfg {
   static constexpr int C = 32, IR = FB_TR + 2, IC = FB_TC + 2, CV = C / 4, NP = 2, PS = 80, NT = 2, KS = 9;
@@ -140,11 +110,8 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
   const int li = lane & 15, lg = lane >> 4, tq = li >> 2, tp = li & 3;
   const int ah = wave >> 1, bh = wave & 1;   // dW: this wave's (ci half, co half)
   const int tiles_x = (a.wv + FB_TC - 1) / FB_TC, tiles_y = (a.hv + FB_TR - 1) / FB_TR;
-  const int ntiles = a.n * tiles_y * tiles_x;
-  const int nxcd = (gridDim.x % 8 == 0) ? 8 : 1;
-  const int xcd = blockIdx.x % nxcd, rank = blockIdx.x / nxcd, per = gridDim.x / nxcd;
-  const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
-  const int d_tx = per % tiles_x, d_ty = (per / tiles_x) % tiles_y, d_n = per / (tiles_x * tiles_y);
+  int rank, per, t_lo, t_hi, d_tx, d_ty, d_n;   // this workgroup's tiles: t_lo + rank, + per, ... < t_hi
+  fbc_tile_share(a.n, tiles_y, tiles_x, rank, per, t_lo, t_hi, d_tx, d_ty, d_n);
 
   // ---- halo items of this thread (conv_f16x2_kernel's, 256 threads): item it = float4 vv of halo pixel pix = p0 + 32 it, p0 = thread / 8.
   // Nothing per item is kept in registers: row / column follow from p0 and compile-time constants (32 it = 18 A + B), the LDS address
@@ -172,9 +139,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
     int iy0, ix0, off0;
   };
   auto pf_make = [&](int n, int ty, int tx, bool live) -> Pf {
-#ifdef FB_KO_LOAD   // (diagnostic: every halo load reads tile (1, 1) of sample 0 - cache hits)
-    n = 0, ty = 1, tx = 1;
-#endif
     Pf f;
     f.iy0 = ty * FB_TR - 1;
     f.ix0 = tx * FB_TC - 1;
@@ -225,7 +189,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
         v.x *= act_grad_from_out(q.x, INACT), v.y *= act_grad_from_out(q.y, INACT);
         v.z *= act_grad_from_out(q.z, INACT), v.w *= act_grad_from_out(q.w, INACT);
       }
-#ifndef FB_KO_INSIDE   // (diagnostic: padding is not zeroed - WRONG at the image border; what the selects cost)
       // (padding must not be staged as k0.  Knock-out: these selects are 4 - 5 % of the forms with channel sums, the bias sums below
       //  2 - 3 %; skipping them behind a workgroup-uniform "the whole halo lies inside the image" branch was measured SLOWER
       //  (151.7 -> 154.2 us: the branch splits the block the riding arithmetic is scheduled in) - they stay unconditional)
@@ -233,7 +196,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
         const bool inside = off < f.bytes;
         v = inside ? v : make_float4(0.f, 0.f, 0.f, 0.f);
       }
-#endif
       if (GST) {
         const u32x4 sv = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
         __builtin_amdgcn_raw_buffer_store_b128(sv, bx_rsrc(a.gnb_out + (f.x - a.x), f.bytes), item_own(it) ? off : BX_OOB, 0, 0);
@@ -244,12 +206,10 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
       v.z *= act_grad_from_out(q.z, INACT), v.w *= act_grad_from_out(q.w, INACT);
     }
     pre[it] = v;
-#ifndef FB_KO_BSUM   // (diagnostic: no bias gradient - what its selects and adds cost)
     {   // (bias gradient: the pixels this tile owns; a select, not a branch)
       const bool own = item_own(it);
       bsum.x += own ? v.x : 0.f, bsum.y += own ? v.y : 0.f, bsum.z += own ? v.z : 0.f, bsum.w += own ? v.w : 0.f;
     }
-#endif
     m = __builtin_fmaxf(__builtin_fmaxf(m, fabsf(v.x)), fabsf(v.y));
     m = __builtin_fmaxf(__builtin_fmaxf(m, fabsf(v.z)), fabsf(v.w));
   };
@@ -272,18 +232,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
     const float x_[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
     f32x2 v_[4], r_[4];
     f16x2_t h1_[4], h2_[4];
-#ifdef FB_KO_SPLIT   // (diagnostic: the staged bits are not the split - WRONG results; what the split's instructions cost)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int idx = (int)threadIdx.x + (it + j) * NTHR;
-      unsigned short* p = xh + lds_item + (it + j) * (32 * PS);
-      if ((it + j + 1) * NTHR > K::NITEMS) p = idx < K::NITEMS ? p : pad16 - C;
-      *(uint2*)(p) = make_uint2(__float_as_uint(x_[4 * j]) & 0x3fff3fffu, __float_as_uint(x_[4 * j + 1]) & 0x3fff3fffu);
-      *(uint2*)(p + C) = make_uint2(__float_as_uint(x_[4 * j + 2]) & 0x3fff3fffu, __float_as_uint(x_[4 * j + 3]) & 0x3fff3fffu);
-    }
-    (void)sc; (void)v_; (void)r_; (void)h1_; (void)h2_;
-    return;
-#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) v_[k] = (f32x2){x_[2 * k] * sc, x_[2 * k + 1] * sc};
 #pragma unroll
@@ -304,11 +252,7 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
 
   int tile = t_lo + rank;
   int cn = 0, cty = 0, ctx = 0;
-  auto advance = [&](int& n_, int& ty_, int& tx_) {
-    tx_ += d_tx, ty_ += d_ty, n_ += d_n;
-    if (tx_ >= tiles_x) tx_ -= tiles_x, ++ty_;
-    if (ty_ >= tiles_y) ty_ -= tiles_y, ++n_;
-  };
+  auto advance = [&](int& n_, int& ty_, int& tx_) { fbc_advance(n_, ty_, tx_, d_n, d_ty, d_tx, tiles_y, tiles_x); };
 
   // ---- centre operands: this lane's 8 pieces (row MT wave + mt, column li, channels 16 nt + 4 lg ..) of x (fetched one tile ahead: its
   // values are staged at the top of the tile) and of the epilogue's operands - gx so far (ACCUM), the GroupNorm input of the channel
@@ -318,9 +262,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
   float4 cxw[NPIECE], cy[ACCUM ? NPIECE : 1], cab[EPIAB && XSRC != 1 ? NPIECE : 1], cact[EPIACT && XSRC != 2 ? NPIECE : 1];
   const float* wx_base = XSRC == 1 ? a.ab_x : (XSRC == 2 ? a.ab_act_y : fa_.wx);
   auto centre_off = [&](int ty, int tx, unsigned (&off)[MT]) {
-#ifdef FB_KO_LOAD
-    ty = 1, tx = 1;
-#endif
     const int vy0 = ty * FB_TR + wave * MT, vx0 = tx * FB_TC + li;
     const int t0 = (ty * FB_TR * a.wf + tx * FB_TC) * (C * 4) + y_lane;
 #pragma unroll
@@ -397,8 +338,8 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
       unsigned pl[2][4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float v0 = fb_weight(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j, co);
-        const float v1 = fb_weight(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j + 1, co);
+        const float v0 = fbc_weight<32>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j, co);
+        const float v1 = fbc_weight<32>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j + 1, co);
         f2_split_pair(v0 * sw, v1 * sw, pl[0][j], pl[1][j]);
       }
 #pragma unroll
@@ -438,11 +379,7 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float va = sA[nt][r], vb = sB[nt][r];
-#define FB_ROW(ctrl)                                                                                \
-  va += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(va), ctrl, 0xf, 0xf, true)); \
-  vb += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(vb), ctrl, 0xf, 0xf, true));
-        FB_ROW(0xB1) FB_ROW(0x4E) FB_ROW(0x124) FB_ROW(0x128)
-#undef FB_ROW
+        fbc_row_sum2(va, vb);
         if (li == 0) {
           abw[wave * 2 * C + nt * 16 + lg * 4 + r] = va;
           abw[wave * 2 * C + C + nt * 16 + lg * 4 + r] = vb;
@@ -467,8 +404,7 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
   };
 
   const int xa_lane = (wave * MT * IC + li) * PS + lg * 8;
-  constexpr int PA[3] = {1, 0, 0};
-  constexpr int PB[3] = {0, 1, 0};
+  using PO = FbcOrder2;   // the three products of a k-step
 
   // ---- one tile: TOP (final values + maxima | barrier A | exponents | halo and x tile split and staged, next tile requested |
   // barrier B), D (the input gradient's 216 products per wave), W (its epilogue + this wave's 216 dW products over the WHOLE tile).
@@ -497,14 +433,7 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
     }
     if (XGN && cn != xg_n) {
       xg_n = cn;
-      float mean, rstd;
-      gn_moments(fa_.wx_gn_stats, cn, (double)a.hf * a.wf * C, fa_.wx_gn_eps, &mean, &rstd);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const float4 g_ = *(const float4*)(fa_.wx_gn_gamma + nt * 16 + lg * 4), b_ = *(const float4*)(fa_.wx_gn_beta + nt * 16 + lg * 4);
-        xg_sc[nt] = make_float4(rstd * g_.x, rstd * g_.y, rstd * g_.z, rstd * g_.w);
-        xg_sh[nt] = make_float4(b_.x - xg_sc[nt].x * mean, b_.y - xg_sc[nt].y * mean, b_.z - xg_sc[nt].z * mean, b_.w - xg_sc[nt].w * mean);
-      }
+      fbc_gn_affine<NT>(fa_, cn, (double)a.hf * a.wf * C, lg, xg_sc, xg_sh);
     }
     if (!RIDE) {
       prep_cf(cn);
@@ -540,7 +469,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
   auto rest = [&]() __attribute__((always_inline)) {
     // ---- staging: the halo with its own per-tile scale, x with 2^(S - sx_e) (a term of dW carries 2^S; where the halo or the x tile
     // is all zero the exponent does not matter)
-#ifndef FB_KO_STAGE   // (diagnostic: nothing is staged - what the phase costs; WRONG results)
     {
       const float sc = __builtin_ldexpf(1.f, sx_e);
       // (one wave per SIMD: nothing hides the latency of a dependent vector instruction, and the compiler keeps source order - the
@@ -577,7 +505,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
         }
       }
     }
-#endif
     FB_T(9)
     // this tile's epilogue operands are requested now (used after D); the next tile's halo and x strip ride in D's first k-steps (a
     // wave issues one 1-KB load per ~16 cycles at best: 19 - 30 of them in a row cost ~2 k cycles per tile in front of barrier B)
@@ -616,7 +543,7 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
       };
       load_rows(0, 0, MT + 2);
       load_w(0, fw[0]);
-      fb_static_for<0, KS>([&](auto ksc) __attribute__((always_inline)) {
+      fbc_static_for<0, KS>([&](auto ksc) __attribute__((always_inline)) {
         constexpr int ks = decltype(ksc)::value;
         constexpr int kx = ks / 3, ky = ks % 3, b = ks & 1;
         if (ks + 1 < KS) load_w(ks + 1, fw[b ^ 1]);
@@ -640,13 +567,10 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
                   acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                      __builtin_bit_cast(f16x8_t, fw[b][PB[q]][nt]), __builtin_bit_cast(f16x8_t, R[ky + mt][PA[q]]),
+                      __builtin_bit_cast(f16x8_t, fw[b][PO::PB[q]][nt]), __builtin_bit_cast(f16x8_t, R[ky + mt][PO::PA[q]]),
                       (ks == 0 && q == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[mt][nt], 0, 0, 0);   // (the first product starts from a zero literal)
               }
         };
-#ifdef FB_KO_D   // (diagnostic: no input-gradient products)
-        if (false)
-#endif
         if (ky == 0 && kx > 0) {
           mm(0, 2);
           __builtin_amdgcn_sched_barrier(0);
@@ -665,28 +589,12 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
     auto epi_piece = [&](int i) __attribute__((always_inline)) {
       const int mt = i / NT, nt = i % NT;
       const float livef = cur_off[mt] != BX_OOB ? 1.f : 0.f;
-      f32x4 o = acc[mt][nt] * desc;
-      if (ACCUM) {
-        const float4 q = cy[ACCUM ? i : 0];
-        o += (f32x4){q.x, q.y, q.z, q.w};
-      }
-      if (EPIACT) {
-        const float4 q = XSRC == 2 ? cxw[i] : cact[EPIACT && XSRC != 2 ? i : 0];
-        o *= (f32x4){act_grad_from_out(q.x, EPIACT), act_grad_from_out(q.y, EPIACT), act_grad_from_out(q.z, EPIACT),
-                     act_grad_from_out(q.w, EPIACT)};
-      }
+      const f32x4 o = fbc_epi_value<ACCUM, EPIACT>(acc[mt][nt], desc, cy[ACCUM ? i : 0], XSRC == 2 ? cxw[i] : cact[EPIACT && XSRC != 2 ? i : 0]);
       const u32x4 ov = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
-#ifdef FB_KO_STORE   // (diagnostic: the stores are dropped)
-      __builtin_amdgcn_raw_buffer_store_b128(ov, bx_rsrc(cur_y, y_bytes), (cur_off[mt] + nt * 64) | BX_OOB, 0, 0);
-#else
       __builtin_amdgcn_raw_buffer_store_b128(ov, bx_rsrc(cur_y, y_bytes), cur_off[mt] + nt * 64, 0, 0);
-#endif
       if (EPIAB) {
         const float4 xv = XSRC == 1 ? cxw[i] : cab[EPIAB && XSRC != 1 ? i : 0];
-        const float g0 = o[0] * livef, g1 = o[1] * livef, g2 = o[2] * livef, g3 = o[3] * livef;
-        sA[nt][0] += g0, sA[nt][1] += g1, sA[nt][2] += g2, sA[nt][3] += g3;
-        sB[nt][0] = __builtin_fmaf(g0, xv.x, sB[nt][0]), sB[nt][1] = __builtin_fmaf(g1, xv.y, sB[nt][1]);
-        sB[nt][2] = __builtin_fmaf(g2, xv.z, sB[nt][2]), sB[nt][3] = __builtin_fmaf(g3, xv.w, sB[nt][3]);
+        fbc_ab_add(o, livef, xv, sA[nt], sB[nt]);
       }
     };
 
@@ -703,7 +611,7 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
       auto load_x = [&](int ks, s16x8 (&F)[NP]) __attribute__((always_inline)) {
         const unsigned short* xq = xt + (2 * ks * FB_TC + 4 * lg + tq) * PS + ah * 16 + tp * 4;
 #pragma unroll
-        for (int p = 0; p < NP; ++p) F[p] = fb_tr_read8(xq + p * C, xq + FB_TC * PS + p * C);
+        for (int p = 0; p < NP; ++p) F[p] = fbc_tr_read8(xq + p * C, xq + FB_TC * PS + p * C);
       };
       // KX1: the kx = 1 fragments are assembled from the kx = 0 and kx = 2 ones (a one-pixel shift of the same rows: two
       // v_alignbit_b32 per 4 pixels) instead of being read - 20 of 28 transposing reads per k-step.  Same-box A/B per form
@@ -718,7 +626,7 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
           if (FB_KX1_ALIGN && kx == 1) continue;
           const unsigned short* gq = xh + (row0 * IC + (4 * lg + tq) + 2 - kx) * PS + bh * 16 + tp * 4;
 #pragma unroll
-          for (int p = 0; p < NP; ++p) G[kx][p] = fb_tr_read8(gq + p * C, gq + IC * PS + p * C);
+          for (int p = 0; p < NP; ++p) G[kx][p] = fbc_tr_read8(gq + p * C, gq + IC * PS + p * C);
         }
         if (FB_KX1_ALIGN) {
           // a lane's 4 + 4 values of a fragment are pixels q .. q + 3 of rows row0, row0 + 1 (q = 4 lg + 2 - kx): kx = 2 holds
@@ -740,40 +648,31 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
         for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
           for (int q = 0; q < 3; ++q)
-            accw[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, fx[ks & 1][PA[q]]),
-                                                                       __builtin_bit_cast(f16x8_t, G[kx][PB[q]]), accw[ky * 3 + kx], 0, 0, 0);
+            accw[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, fx[ks & 1][PO::PA[q]]),
+                                                                       __builtin_bit_cast(f16x8_t, G[kx][PO::PB[q]]), accw[ky * 3 + kx], 0, 0, 0);
       };
       load_x(0, fx[0]);
       load_pair(0, G0[1]);   // (k-step 0, ky = 2)
       load_pair(2, G0[0]);   // (k-step 0, ky = 0)
-#ifdef FB_KO_W   // (diagnostic: no dW products / reads; the epilogue and the riding work stay)
-#define FB_MM3(a_, b_, c_)
-#define FB_LP(a_, b_)
-#define FB_LX(a_, b_)
-#else
-#define FB_MM3(a_, b_, c_) mm3(a_, b_, c_)
-#define FB_LP(a_, b_) load_pair(a_, b_)
-#define FB_LX(a_, b_) load_x(a_, b_)
-#endif
-      fb_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) {
+      fbc_static_for<0, 8>([&](auto kc) __attribute__((always_inline)) {
         constexpr int ks = decltype(kc)::value;
         // ky = 2 (the pair fetched for ky = 0 of the previous k-step); the odd pair of this k-step is fetched under it
-        FB_LP(2 * ks + 1, G1);
+        load_pair(2 * ks + 1, G1);
         if (ks < NPIECE / 2) epi_piece(2 * ks);       // (the input gradient's epilogue rides in the first k-steps: its stores leave early)
-        FB_MM3(ks, 2, G0[(ks + 1) & 1]);
+        mm3(ks, 2, G0[(ks + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
         // ky = 0; the next k-step's x^T fragments are fetched under it
-        if (ks + 1 < 8) FB_LX(ks + 1, fx[(ks + 1) & 1]);
+        if (ks + 1 < 8) load_x(ks + 1, fx[(ks + 1) & 1]);
         if (ks < NPIECE / 2) epi_piece(2 * ks + 1);
-        FB_MM3(ks, 0, G0[ks & 1]);
+        mm3(ks, 0, G0[ks & 1]);
         __builtin_amdgcn_sched_barrier(0);
         // ky = 1; the next k-step's even pair is fetched under it (into the set ky = 2 has just left)
-        if (ks + 1 < 8) FB_LP(2 * ks + 4, G0[(ks + 1) & 1]);
+        if (ks + 1 < 8) load_pair(2 * ks + 4, G0[(ks + 1) & 1]);
         if (XSH && ks < NPIECE / 2) x_issue(n1, ty1, tx1, tile + per < t_hi, 2 * ks, 2 * ks + 2);   // (behind the epilogue's pieces 2 ks, 2 ks + 1)
 #pragma unroll
         for (int it = 0; it < NLOAD; ++it)
           if (RIDE && it * 8 / NLOAD == ks) prep_item(pfn, it, mg_next);   // the next tile's halo items (requested in D) become final
-        FB_MM3(ks, 1, G1);
+        mm3(ks, 1, G1);
         __builtin_amdgcn_sched_barrier(0);
       });
     }
@@ -785,10 +684,6 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
     if (RIDE) mg_lane = mg_next;
   };
 
-#ifdef FB_STAGGER   // (diagnostic: every second workgroup starts its tile loop FB_STAGGER x 64 cycles late - are the workgroups' phases, all
-                    //  requesting their next tile at the same time, what the loads wait for?  Measured with 60 and 110: 135 - 146 us either way, same box)
-  if (rank & 1) __builtin_amdgcn_s_sleep(FB_STAGGER);
-#endif
   int flushed = 0;
   bool resume = false;
   float* out = fa_.part + (long)blockIdx.x * (9 * C * C);
@@ -816,8 +711,8 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
         need = true;
         break;
       }
-      if (!s_set && adds) {   // the first tile with something to add sets the exponent, FB_SMARGIN bits of headroom
-        S_w = ex_e + sx_e - FB_SMARGIN;
+      if (!s_set && adds) {   // the first tile with something to add sets the exponent, FBC_SMARGIN bits of headroom
+        S_w = ex_e + sx_e - FBC_SMARGIN;
         s_set = true;
       }
       rest();
@@ -858,46 +753,14 @@ __global__ __launch_bounds__(256) void conv_bwd_fused_kernel(FbArgs fa_) {
 
 // Launch: hipErrorInvalidValue when no instance exists for the combination (the caller keeps the two launches).
 hipError_t dis_fb_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream) {
-  using K = FbCfg;
-  const ConvArgs& a = f.c;
-  static bool attr_set[16] = {};
-  auto launch = [&](auto kern, int slot) -> hipError_t {
-    if (!attr_set[slot]) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-      if (e != hipSuccess) return e;
-      attr_set[slot] = true;
-    }
-    DIS_TAG("conv_bwd_fused_kernel<32>");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NTHR), K::LDS_BYTES, stream, f);
-    return hipSuccess;
-  };
-  constexpr int S = DIS_ACT_SELU;
+  static bool attr_set[FBC_NFORMS] = {};
+  const char* tag = "conv_bwd_fused_kernel<32>";
 #ifdef FB_ONLY   // (diagnostic builds: one instance, e.g. -DFB_ONLY=0,false,false,false,0,0,false,false - resource reports, ISA studies)
-  return launch(conv_bwd_fused_kernel<FB_ONLY>, 0);
+  return fbc_launch<FbCfg>(conv_bwd_fused_kernel<FB_ONLY>, attr_set[0], tag, f, grid, stream);
 #endif
-  if (inact != 0 && inact != S) return hipErrorInvalidValue;
-  const bool coef = a.gnb_coef != nullptr, gst = a.gnb_out != nullptr, ab = a.ab_out != nullptr, epiact = a.ab_act_y != nullptr;
-  if (!coef) {
-    // plain operand (gy itself, or gy act'(y)): no epilogue forms
-    if (ab || gst || xgn || xsrc) return hipErrorInvalidValue;
-    if (a.accum) return inact ? launch(conv_bwd_fused_kernel<S, false, true, false, 0, 0, false, false>, 0)
-                              : launch(conv_bwd_fused_kernel<0, false, true, false, 0, 0, false, false>, 1);
-    return inact ? launch(conv_bwd_fused_kernel<S, false, false, false, 0, 0, false, false>, 2)
-                 : launch(conv_bwd_fused_kernel<0, false, false, false, 0, 0, false, false>, 3);
-  }
-  if (ab && !a.accum && !epiact && xsrc == 1 && xgn) {   // conv2d_gn_in: the GroupNorm input of the sums is the conv's input
-    if (gst) return inact ? hipErrorInvalidValue : launch(conv_bwd_fused_kernel<0, true, false, true, 0, 1, true, true>, 4);
-    return inact ? launch(conv_bwd_fused_kernel<S, true, false, true, 0, 1, true, false>, 5)
-                 : launch(conv_bwd_fused_kernel<0, true, false, true, 0, 1, true, false>, 6);
-  }
-  if (gst || xgn) return hipErrorInvalidValue;
-  if (ab && a.accum && epiact && xsrc == 2 && inact == S)   // ResNetBlock chain: x = SELU(GroupNorm(x2) + res) is the conv's input
-    return launch(conv_bwd_fused_kernel<S, true, true, true, S, 2, false, false>, 7);
-  if (ab && a.accum && !epiact && xsrc == 0 && inact == S)  // two-consumer GroupNorm output (Block2D3D conv1_1)
-    return launch(conv_bwd_fused_kernel<S, true, true, true, 0, 0, false, false>, 8);
-  if (!ab && a.accum && xsrc == 0 && inact == S) return launch(conv_bwd_fused_kernel<S, true, true, false, 0, 0, false, false>, 9);
-  if (!ab && !a.accum && xsrc == 0)
-    return inact ? launch(conv_bwd_fused_kernel<S, true, false, false, 0, 0, false, false>, 10)
-                 : launch(conv_bwd_fused_kernel<0, true, false, false, 0, 0, false, false>, 11);
-  return hipErrorInvalidValue;
+  return fbc_dispatch(f.c, inact, xgn, xsrc, [&](auto form) {
+    using F = decltype(form);
+    return fbc_launch<FbCfg>(conv_bwd_fused_kernel<F::INACT, F::INCOEF, F::ACCUM, F::EPIAB, F::EPIACT, F::XSRC, F::XGN, F::GST>,
+                             attr_set[F::SLOT], tag, f, grid, stream);
+  });
 }

@@ -23,27 +23,7 @@
 // The two kh halves of a (ci half, co half) are added once at the end of the launch (kh 0 + kh 1, fixed order), and the workgroup's
 // slab is summed over workgroups by wgrad_reduce_kernel (fixed order, fp64): no float atomics, bit-reproducible.
 // LDS: weights 55.3 KB + halo 40.3 KB + x tile 28.7 KB = 124.3 KB.
-#include "conv_args.h"
-#include <type_traits>
-
-typedef short f3_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x8 f3_tr_read8(const unsigned short* p0, const unsigned short* p1) {
-  const f3_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) f3_s16x4*)p0);
-  const f3_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) f3_s16x4*)p1);
-  return (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-// conv2d.hip's bx_weight for 32 channels, mode 1 (input gradient: flipped taps, transposed)
-__device__ __forceinline__ float f3_weight(const float* w, int stride_row, int wo, int wi, int ks, int lg, int j, int co) {
-  const int c = 8 * lg + j;
-  return (c < wo && co < wi) ? w[c * stride_row + co * 9 + (8 - ks)] : 0.f;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void f3_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    f3_static_for<I + 1, N>(f);
-  }
-}
+#include "conv_bwd_fused_common.h"
 
 struct F3Cfg {
   static constexpr int C = 32, TR = 8, TC = 16, IR = TR + 2, IC = TC + 2, CV = C / 4, NP = 3, NT = 2, KS = 9;
@@ -76,6 +56,8 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
   const int li = lane & 15, lg = lane >> 4, tq = li >> 2, tp = li & 3;
   const int kh = wave >> 2, ah = (wave >> 1) & 1, bh = wave & 1;   // dW: this wave's (row half, ci half, co half)
   const int tiles_x = (a.wv + TC - 1) / TC, tiles_y = (a.hv + TR - 1) / TR;
+  // (fbc_tile_share's and fbc_advance's arithmetic, spelled out: through either helper the compiler allocates this kernel's scalar
+  //  registers differently - profiles/r9_bwd_fused_shared.md - and the device code of this family is held to the byte)
   const int ntiles = a.n * tiles_y * tiles_x;
   const int nxcd = (gridDim.x % 8 == 0) ? 8 : 1;
   const int xcd = blockIdx.x % nxcd, rank = blockIdx.x / nxcd, per = gridDim.x / nxcd;
@@ -151,8 +133,8 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
       unsigned pl[NP][4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float v0 = f3_weight(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j, co);
-        const float v1 = f3_weight(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j + 1, co);
+        const float v0 = fbc_weight<32>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j, co);
+        const float v1 = fbc_weight<32>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j + 1, co);
         split3_pair(v0, v1, pl[0][j], pl[1][j], pl[2][j]);
       }
 #pragma unroll
@@ -171,9 +153,7 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
 #pragma unroll
   for (int nt = 0; nt < (XGN ? NT : 1); ++nt) xg_sc[nt] = xg_sh[nt] = make_float4(0.f, 0.f, 0.f, 0.f);
 
-  // smallest terms first (conv_bf16x3_kernel's order)
-  constexpr int PA[6] = {2, 1, 0, 1, 0, 0};
-  constexpr int PB[6] = {0, 1, 2, 0, 1, 0};
+  using PO = FbcOrder3;   // the six products of a k-step
   const int xa_lane = (wave * IC + li) * PS + lg * 8;
   const int lds_vv = ((int)threadIdx.x % CV) * 4;
 
@@ -182,14 +162,7 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
     float* cur_y = a.y + (long)cn * a.hf * a.wf * C;
     if (XGN && cn != xg_n) {
       xg_n = cn;
-      float mean, rstd;
-      gn_moments(fa_.wx_gn_stats, cn, (double)a.hf * a.wf * C, fa_.wx_gn_eps, &mean, &rstd);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const float4 g_ = *(const float4*)(fa_.wx_gn_gamma + nt * 16 + lg * 4), b_ = *(const float4*)(fa_.wx_gn_beta + nt * 16 + lg * 4);
-        xg_sc[nt] = make_float4(rstd * g_.x, rstd * g_.y, rstd * g_.z, rstd * g_.w);
-        xg_sh[nt] = make_float4(b_.x - xg_sc[nt].x * mean, b_.y - xg_sc[nt].y * mean, b_.z - xg_sc[nt].z * mean, b_.w - xg_sc[nt].w * mean);
-      }
+      fbc_gn_affine<NT>(fa_, cn, (double)a.hf * a.wf * C, lg, xg_sc, xg_sh);
     }
     // barrier A: every wave has finished the previous tile (and, first tile, the weight split has read its fp32 copy)
     __syncthreads();
@@ -272,7 +245,7 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
       };
       load_rows(0);
       load_w(0, fw[0]);
-      f3_static_for<0, KS>([&](auto ksc) __attribute__((always_inline)) {
+      fbc_static_for<0, KS>([&](auto ksc) __attribute__((always_inline)) {
         constexpr int ks = decltype(ksc)::value;
         constexpr int kx = ks / 3, ky = ks % 3, b = ks & 1;
         if (ks + 1 < KS) {
@@ -283,8 +256,8 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
         for (int q = 0; q < 6; ++q)
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt)
-            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fw[b][PB[q]][nt]),
-                                                              __builtin_bit_cast(bf16x8, R[kx & 1][ky][PA[q]]), acc[nt], 0, 0, 0);
+            acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fw[b][PO::PB[q]][nt]),
+                                                              __builtin_bit_cast(bf16x8, R[kx & 1][ky][PO::PA[q]]), acc[nt], 0, 0, 0);
       });
       // epilogue (conv_bf16x3_kernel's with no bias and no activation: acc, + the old value when accumulating)
 #pragma unroll
@@ -302,12 +275,12 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
     // ---------------- weight gradient: this wave's 9 tap tiles over tile rows 4 kh .. 4 kh + 3: 2 k-steps of 32 pixels (rows 2 ks,
     // 2 ks + 1), x^T fragments (three planes) against the gy fragments of the 9 tap shifts - centre pixel (r', c') meets the halo pixel
     // (r' + 2 - ky, c' + 2 - kx)
-    f3_static_for<0, 2>([&](auto sc) __attribute__((always_inline)) {
+    fbc_static_for<0, 2>([&](auto sc) __attribute__((always_inline)) {
       const int ks = 2 * kh + decltype(sc)::value;
       s16x8 fx[NP];
       const unsigned short* xq = xt + (2 * ks * TC + 4 * lg + tq) * PS + ah * 16 + tp * 4;
 #pragma unroll
-      for (int p = 0; p < NP; ++p) fx[p] = f3_tr_read8(xq + p * C, xq + TC * PS + p * C);
+      for (int p = 0; p < NP; ++p) fx[p] = fbc_tr_read8(xq + p * C, xq + TC * PS + p * C);
       s16x8 G[2][3][NP];   // [ky parity][kx][plane]
       auto load_g = [&](int ky, s16x8 (&Gk)[3][NP]) __attribute__((always_inline)) {
         const int row0 = 2 * ks + 2 - ky;
@@ -315,19 +288,19 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
         for (int kx = 0; kx < 3; ++kx) {
           const unsigned short* gq = xh + (row0 * IC + (4 * lg + tq) + 2 - kx) * PS + bh * 16 + tp * 4;
 #pragma unroll
-          for (int p = 0; p < NP; ++p) Gk[kx][p] = f3_tr_read8(gq + p * C, gq + IC * PS + p * C);
+          for (int p = 0; p < NP; ++p) Gk[kx][p] = fbc_tr_read8(gq + p * C, gq + IC * PS + p * C);
         }
       };
       load_g(0, G[0]);
-      f3_static_for<0, 3>([&](auto kyc) __attribute__((always_inline)) {
+      fbc_static_for<0, 3>([&](auto kyc) __attribute__((always_inline)) {
         constexpr int ky = decltype(kyc)::value;
         if (ky + 1 < 3) load_g(ky + 1, G[(ky + 1) & 1]);
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
           for (int q = 0; q < 6; ++q)
-            accw[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fx[PA[q]]),
-                                                                        __builtin_bit_cast(bf16x8, G[ky & 1][kx][PB[q]]), accw[ky * 3 + kx], 0, 0, 0);
+            accw[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, fx[PO::PA[q]]),
+                                                                        __builtin_bit_cast(bf16x8, G[ky & 1][kx][PO::PB[q]]), accw[ky * 3 + kx], 0, 0, 0);
       });
     });
 
@@ -367,23 +340,12 @@ __global__ __launch_bounds__(512) void conv_bwd_fused_bf16x3_kernel(FbArgs fa_) 
 }
 
 // Launch: hipErrorInvalidValue when no instance exists for the combination (the caller keeps the two launches).
-hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, long grid, hipStream_t stream) {
-  using K = F3Cfg;
-  const ConvArgs& a = f.c;
+hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream) {
   static bool attr_set[5] = {};
-  auto launch = [&](auto kern, int slot) -> hipError_t {
-    if (!attr_set[slot]) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-      if (e != hipSuccess) return e;
-      attr_set[slot] = true;
-    }
-    DIS_TAG("conv_bwd_fused_bf16x3_kernel<32>");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NTHR), K::LDS_BYTES, stream, f);
-    return hipSuccess;
-  };
+  auto launch = [&](auto kern, int slot) { return fbc_launch<F3Cfg>(kern, attr_set[slot], "conv_bwd_fused_bf16x3_kernel<32>", f, grid, stream); };
   constexpr int S = DIS_ACT_SELU;
-  if (inact != 0 && inact != S) return hipErrorInvalidValue;
-  if (xgn) return (inact || a.accum) ? hipErrorInvalidValue : launch(conv_bwd_fused_bf16x3_kernel<0, false, true>, 0);
-  if (a.accum) return inact ? launch(conv_bwd_fused_bf16x3_kernel<S, true, false>, 1) : launch(conv_bwd_fused_bf16x3_kernel<0, true, false>, 2);
+  if ((inact != 0 && inact != S) || xsrc != 0) return hipErrorInvalidValue;
+  if (xgn) return (inact || f.c.accum) ? hipErrorInvalidValue : launch(conv_bwd_fused_bf16x3_kernel<0, false, true>, 0);
+  if (f.c.accum) return inact ? launch(conv_bwd_fused_bf16x3_kernel<S, true, false>, 1) : launch(conv_bwd_fused_bf16x3_kernel<0, true, false>, 2);
   return inact ? launch(conv_bwd_fused_bf16x3_kernel<S, false, false>, 3) : launch(conv_bwd_fused_bf16x3_kernel<0, false, false>, 4);
 }

@@ -1,56 +1,33 @@
-// Input gradient AND weight gradient of a 3x3 stride-1 pad-1 convolution CX -> CG with 16 channels on a side in ONE launch: the
-// sibling of conv_bwd_fused.hip (32 -> 32), same idea, same arithmetic.  Written over both channel counts; only (CX, CG) = (16, 16) is
-// instantiated, tested and measured (profiles/r7_bwd_fused_c16.md) - (16, 32) and (32, 16) keep their two launches.
+// Input gradient AND weight gradient of a 3x3 stride-1 pad-1 convolution 16 -> 16 in ONE launch: the sibling of conv_bwd_fused.hip
+// (32 -> 32), same idea, same arithmetic (profiles/r7_bwd_fused_c16.md).  The mixed shapes (16, 32) and (32, 16) have no kernel here and
+// keep their two launches.  CG = 16 channels of gy (the conv's output), CX = 16 channels of x and gx (the conv's input):
 //     gx[q][ci]        = sum_tap sum_co gy[q + 1 - tap][co] W[co][ci][tap]          (contraction over the CG channels of gy, per tile)
 //     dW[tap][ci][co]  = sum_q'  x[q'][ci] gy[q' + 1 - tap][co]                     (contraction over the pixels q' a tile OWNS)
 // The 18 x 18 gy halo a tile of the input gradient stages in LDS (two fp16 planes, per-tile scale) feeds both products; x and gy are
-// read once.  gx is BIT-identical to conv_f16x2_kernel<CG, CX>'s: the same split, the same per-tile power-of-two scale, the same
-// k-steps in the same order - for CG = 16 the five tap-PAIR k-steps of F2Cfg (k-step ks holds taps 2 ks and 2 ks + 1 in the k-slots
-// of lane groups 0, 1 and 2, 3; the tenth slot is zero), for CG = 32 the nine taps, kx outer.
+// read once.  gx is BIT-identical to conv_f16x2_kernel<16, 16>'s: the same split, the same per-tile power-of-two scale, the same
+// k-steps in the same order - the five tap-PAIR k-steps of F2Cfg (k-step ks holds taps 2 ks and 2 ks + 1 in the k-slots of lane
+// groups 0, 1 and 2, 3; the tenth slot is zero).
 //
 // What differs from the 32 -> 32 kernel:
-//   * dW is 9 x (CX / 16) x (CG / 16) accumulator tiles in all (9 or 18).  There is no channel block to hand to each wave, so the
-//     PIXELS are split: wave w forms every tile over the tile rows 4 w .. 4 w + 3 it owns in the input gradient as well (two k-steps
-//     of 32 pixels), and the four waves' accumulators are added once per workgroup through LDS, in a fixed order, before the slab is
-//     written.  The running dW exponent S (workgroup-uniform, leave-the-loop rescale) is the 32 -> 32 kernel's.
-//   * (16, 16) needs 66 KB of LDS and fits 256 registers: TWO workgroups per CU (__launch_bounds__(256, 2)), i.e. two waves per SIMD,
-//     so one workgroup's staging and epilogue issue under the other's products; the grid is 2 x #CUs and the channel sums take
-//     2 x #CUs slots per sample (FbArgs::c.ab_slots is given by the caller).  The mixed shapes would need 93 - 95 KB: one workgroup per CU.
-#include "conv_args.h"
-#include <type_traits>
-
-typedef short fc_s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x8 fc_tr_read8(const unsigned short* p0, const unsigned short* p1) {
-  const fc_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fc_s16x4*)p0);
-  const fc_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) fc_s16x4*)p1);
-  return (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-// the tap / channel -> k-slot map of conv_f16x2.hip's f2_weight<CG, CX>, input-gradient order (flipped taps, transposed): k-step
-// `ks` is a tap (CG = 32) or the tap pair 2 ks, 2 ks + 1 (CG = 16)
-template <int CG>
-__device__ __forceinline__ float fc_weight(const float* w, int stride_row, int wo, int wi, int ks, int lg, int j, int co) {
-  const int tap = CG == 32 ? ks : 2 * ks + (lg >> 1);
-  const int c = CG == 32 ? 8 * lg + j : 8 * (lg & 1) + j;
-  if (tap > 8) return 0.f;
-  return (c < wo && co < wi) ? w[c * stride_row + co * 9 + (8 - tap)] : 0.f;
-}
-template <int I, int N, class F>
-__device__ __forceinline__ void fc_static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    fc_static_for<I + 1, N>(f);
-  }
-}
+//   * dW is 9 accumulator tiles in all.  There is no channel block to hand to each wave, so the PIXELS are split: wave w forms every
+//     tile over the tile rows 4 w .. 4 w + 3 it owns in the input gradient as well (two k-steps of 32 pixels), and the four waves'
+//     accumulators are added once per workgroup through LDS, in a fixed order, before the slab is written.  The running dW exponent
+//     S (workgroup-uniform, leave-the-loop rescale) is the 32 -> 32 kernel's.
+//   * 66 KB of LDS and 256 registers: TWO workgroups per CU (__launch_bounds__(256, 2)), i.e. two waves per SIMD, so one workgroup's
+//     staging and epilogue issue under the other's products; the grid is 2 x #CUs and the channel sums take 2 x #CUs slots per sample
+//     (FbArgs::c.ab_slots is given by the caller).
+#include "conv_bwd_fused_common.h"
 
 #define FC_TR 16
 #define FC_TC 16
-#define FC_SMARGIN 6   // bits of headroom the dW exponent keeps when it is (re)set (conv_bwd_fused.hip's FB_SMARGIN)
-template <int CG_, int CX_>
+// (CG = CX = 16 makes NT = NA = NB = 1: the loops and index arithmetic over channel blocks below run once by construction.  They
+//  are the text the kernel was compiled from when it was written over both channel counts, kept so that its device code stays what
+//  was tested and measured.)
 struct FcCfg {
-  static constexpr int CG = CG_, CX = CX_;   // channels of gy (the conv's output) / of x and gx (the conv's input)
+  static constexpr int CG = 16, CX = 16;   // channels of gy (the conv's output) / of x and gx (the conv's input)
   static constexpr int IR = FC_TR + 2, IC = FC_TC + 2, CVG = CG / 4, NP = 2;
-  static constexpr int PSG = CG == 32 ? 80 : 48, PSX = CX == 32 ? 80 : 48;   // LDS pixel strides (F2Cfg::PS)
-  static constexpr int NT = CX / 16, KS = CG == 32 ? 9 : 5;
+  static constexpr int PSG = 48, PSX = 48;   // LDS pixel strides (F2Cfg::PS)
+  static constexpr int NT = CX / 16, KS = 5;   // k-steps of the input gradient: tap pairs
   static constexpr int NA = CX / 16, NB = CG / 16, NACC = 9 * NA * NB;        // dW accumulator tiles per wave: [tap][ci block][co block]
   static constexpr int NW = 4, NTHR = 64 * NW, MT = FC_TR / NW;
   static constexpr int RPR = NTHR / (16 * CVG), NMAIN = (IR + RPR - 1) / RPR;   // halo rows a round of items covers (columns 0 .. 15), such rounds
@@ -59,15 +36,16 @@ struct FcCfg {
   static constexpr int NLOAD = NMAIN + NEDGE, NPIECE = MT * NT;
   static constexpr int SMALL_U16 = 32 + 64 + NW * 2 * CX * 2 + CG + 8;   // red (8 doubles), maxima [parity][gy | x][wave], abw [wave][2 CX] floats, write pad
   static constexpr int LDS_BYTES = (W_U16 + X_U16 + XT_U16 + SMALL_U16) * 2;
-  static constexpr int WPC = LDS_BYTES * 2 <= 160 * 1024 ? 2 : 1;             // workgroups per CU
+  static constexpr int WPC = 2;                                               // workgroups per CU
   static constexpr int PART = 9 * CX * CG;                                    // floats of a weight-gradient slab
 };
 
 // INACT / INCOEF / ACCUM / EPIAB / EPIACT / XSRC / XGN / GST: conv_bwd_fused_kernel's forms (see there).
-template <int CG, int CX, int INACT, bool INCOEF, bool ACCUM, bool EPIAB, int EPIACT, int XSRC, bool XGN, bool GST>
-__global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_kernel(FbArgs fa_) {
-  using K = FcCfg<CG, CX>;
+template <int INACT, bool INCOEF, bool ACCUM, bool EPIAB, int EPIACT, int XSRC, bool XGN, bool GST>
+__global__ __launch_bounds__(256, FcCfg::WPC) void conv_bwd_fused_c16_kernel(FbArgs fa_) {
+  using K = FcCfg;
   const ConvArgs& a = fa_.c;
+  constexpr int CG = K::CG, CX = K::CX;
   constexpr int IC = K::IC, PSG = K::PSG, PSX = K::PSX, NT = K::NT, KS = K::KS, NLOAD = K::NLOAD, NPIECE = K::NPIECE, CVG = K::CVG;
   constexpr int NP = K::NP, MT = K::MT, NW = K::NW, NTHR = K::NTHR, NA = K::NA, NB = K::NB;
   constexpr bool IN2 = INACT != 0 || INCOEF;
@@ -79,7 +57,6 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
   static_assert(EPIACT == 0 || EPIAB, "activation gradient at the output: only with the channel sums");
   static_assert(XSRC == 0 || (XSRC == 1 && EPIAB) || (XSRC == 2 && EPIACT), "shared x operand");
   static_assert(!GST || INCOEF, "gpre store: only where the operand is formed on load");
-  static_assert(!INCOEF || CG == CX, "GroupNorm backward on load: the conv's own output fed the GroupNorm");
   static_assert(K::LDS_BYTES * K::WPC <= 160 * 1024, "LDS budget");
   static_assert(CG * (CX * 9 + 1) * 4 <= K::XT_U16 * 2, "the weight prologue's fp32 scratch aliases the x tile");
   static_assert((NW - 1) * K::NACC * 256 * 4 <= (K::X_U16 + K::XT_U16) * 2, "the dW exchange aliases the halo and the x tile");
@@ -97,11 +74,8 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lg = lane >> 4, tq = li >> 2, tp = li & 3;
   const int tiles_x = (a.wv + FC_TC - 1) / FC_TC, tiles_y = (a.hv + FC_TR - 1) / FC_TR;
-  const int ntiles = a.n * tiles_y * tiles_x;
-  const int nxcd = (gridDim.x % 8 == 0) ? 8 : 1;
-  const int xcd = blockIdx.x % nxcd, rank = blockIdx.x / nxcd, per = gridDim.x / nxcd;
-  const int t_lo = (int)((long)ntiles * xcd / nxcd), t_hi = (int)((long)ntiles * (xcd + 1) / nxcd);
-  const int d_tx = per % tiles_x, d_ty = (per / tiles_x) % tiles_y, d_n = per / (tiles_x * tiles_y);
+  int rank, per, t_lo, t_hi, d_tx, d_ty, d_n;   // this workgroup's tiles: t_lo + rank, + per, ... < t_hi
+  fbc_tile_share(a.n, tiles_y, tiles_x, rank, per, t_lo, t_hi, d_tx, d_ty, d_n);
 
   // ---- halo items of this thread.  Items 0 .. NMAIN - 1 walk the halo's columns 0 .. 15 in bands of RPR rows: thread = (band row
   // rr, column, float4 vv), item it = halo pixel (RPR it + rr, column) - ONE lane-varying offset serves them all, an item adds a
@@ -221,11 +195,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
 
   int tile = t_lo + rank;
   int cn = 0, cty = 0, ctx = 0;
-  auto advance = [&](int& n_, int& ty_, int& tx_) {
-    tx_ += d_tx, ty_ += d_ty, n_ += d_n;
-    if (tx_ >= tiles_x) tx_ -= tiles_x, ++ty_;
-    if (ty_ >= tiles_y) ty_ -= tiles_y, ++n_;
-  };
+  auto advance = [&](int& n_, int& ty_, int& tx_) { fbc_advance(n_, ty_, tx_, d_n, d_ty, d_tx, tiles_y, tiles_x); };
 
   // ---- centre operands: this lane's pieces (row MT wave + mt, column li, channels 16 nt + 4 lg ..) of x (fetched one tile ahead) and
   // of the epilogue's operands - gx so far (ACCUM), the GroupNorm input of the channel sums (EPIAB), the activation output (EPIACT)
@@ -239,7 +209,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) off[mt] = (vx0 < a.wv && vy0 + mt < a.hv) ? (unsigned)(t0 + mt * yrow) : BX_OOB;
   };
-  auto x_issue = [&](int n, int ty, int tx, bool live, int i0 = 0, int i1 = FcCfg<CG, CX>::NPIECE) __attribute__((always_inline)) {
+  auto x_issue = [&](int n, int ty, int tx, bool live, int i0 = 0, int i1 = FcCfg::NPIECE) __attribute__((always_inline)) {
     unsigned off[MT];
     centre_off(ty, tx, off);
     const long sb = (long)n * a.hf * a.wf * CX;
@@ -310,8 +280,8 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
       unsigned pl[2][4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float v0 = fc_weight<CG>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j, co);
-        const float v1 = fc_weight<CG>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j + 1, co);
+        const float v0 = fbc_weight<CG>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j, co);
+        const float v1 = fbc_weight<CG>(ws, row + 1, a.w_o, a.w_i, ks, g, 2 * j + 1, co);
         f2_split_pair(v0 * sw, v1 * sw, pl[0][j], pl[1][j]);
       }
 #pragma unroll
@@ -350,11 +320,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float va = sA[nt][r], vb = sB[nt][r];
-#define FC_ROW(ctrl)                                                                                \
-  va += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(va), ctrl, 0xf, 0xf, true)); \
-  vb += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(vb), ctrl, 0xf, 0xf, true));
-        FC_ROW(0xB1) FC_ROW(0x4E) FC_ROW(0x124) FC_ROW(0x128)
-#undef FC_ROW
+        fbc_row_sum2(va, vb);
         if (li == 0) {
           abw[wave * 2 * CX + nt * 16 + lg * 4 + r] = va;
           abw[wave * 2 * CX + CX + nt * 16 + lg * 4 + r] = vb;
@@ -378,8 +344,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
     }
   };
 
-  constexpr int PA[3] = {1, 0, 0};
-  constexpr int PB[3] = {0, 1, 0};
+  using PO = FbcOrder2;   // the three products of a k-step
 
   // ---- one tile: TOP (maxima | barrier A | exponents | halo and x tile split and staged | barrier B), D (the input gradient's
   // products; the next tile's loads ride in its k-steps), W (its epilogue + this wave's dW products over its four tile rows).
@@ -405,14 +370,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
     }
     if (XGN && cn != xg_n) {
       xg_n = cn;
-      float mean, rstd;
-      gn_moments(fa_.wx_gn_stats, cn, (double)a.hf * a.wf * CX, fa_.wx_gn_eps, &mean, &rstd);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        const float4 g_ = *(const float4*)(fa_.wx_gn_gamma + nt * 16 + lg * 4), b_ = *(const float4*)(fa_.wx_gn_beta + nt * 16 + lg * 4);
-        xg_sc[nt] = make_float4(rstd * g_.x, rstd * g_.y, rstd * g_.z, rstd * g_.w);
-        xg_sh[nt] = make_float4(b_.x - xg_sc[nt].x * mean, b_.y - xg_sc[nt].y * mean, b_.z - xg_sc[nt].z * mean, b_.w - xg_sc[nt].w * mean);
-      }
+      fbc_gn_affine<NT>(fa_, cn, (double)a.hf * a.wf * CX, lg, xg_sc, xg_sh);
     }
     if (LATE) {
       prep_cf(cn);
@@ -474,26 +432,19 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
     __syncthreads();
 
     // ---------------- input gradient: KS k-steps x (MT rows x NT channel blocks) x 3 products, conv_f16x2_kernel's order.
-    // k-step ks multiplies halo pixel (row + ky, column + kx) - CG = 32: tap (ky, kx) = (ks % 3, ks / 3), weights packed tap-major;
-    // CG = 16: lane groups 0, 1 take tap 2 ks, groups 2, 3 tap 2 ks + 1 (the tenth slot's weights are zero; its pixels are tap 8's).
+    // k-step ks multiplies halo pixel (row + ky, column + kx): lane groups 0, 1 take tap 2 ks, groups 2, 3 tap 2 ks + 1 (the tenth
+    // slot's weights are zero; its pixels are tap 8's).
     {
-      const int xa_lane = (wave * MT * IC + li) * PSG + (CG == 32 ? lg * 8 : (lg & 1) * 8);
+      const int xa_lane = (wave * MT * IC + li) * PSG + (lg & 1) * 8;
       const bool hi_tap = (lg >> 1) != 0;
       // ONE fragment set: with two workgroups per CU the other workgroup's wave covers the latency of these reads, and the registers
       // of a second set are what the epilogue forms lack (a spilling instance loses its prefetch to scratch waits).  The reads are
       // issued in the order the products need them (pixel plane 1 x weight plane 0 first).
       s16x8 fa[NP][MT], fw[NP][NT];
       auto load_frag = [&](int ks) __attribute__((always_inline)) {
-        int xoff, wt;
-        if (KS == 9) {
-          const int kx = ks / 3, ky = ks % 3;
-          xoff = (ky * IC + kx) * PSG;
-          wt = ky * 3 + kx;
-        } else {
-          const int t0 = 2 * ks, t1 = 2 * ks + 1 > 8 ? 8 : 2 * ks + 1;
-          xoff = hi_tap ? ((t1 / 3) * IC + t1 % 3) * PSG : ((t0 / 3) * IC + t0 % 3) * PSG;
-          wt = ks;
-        }
+        const int t0 = 2 * ks, t1 = 2 * ks + 1 > 8 ? 8 : 2 * ks + 1;
+        const int xoff = hi_tap ? ((t1 / 3) * IC + t1 % 3) * PSG : ((t0 / 3) * IC + t0 % 3) * PSG;
+        const int wt = ks;
 #pragma unroll
         for (int pp = 0; pp < NP; ++pp) {
           const int pw = pp, pa = NP - 1 - pp;
@@ -503,11 +454,11 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
           for (int mt = 0; mt < MT; ++mt) fa[pa][mt] = *(const s16x8*)(xh + xa_lane + xoff + mt * IC * PSG + pa * CG);
         }
       };
-      fc_static_for<0, KS>([&](auto ksc) __attribute__((always_inline)) {
+      fbc_static_for<0, KS>([&](auto ksc) __attribute__((always_inline)) {
         constexpr int ks = decltype(ksc)::value;
         load_frag(ks);
         // the next tile's loads that ride in this k-step (their registers were emptied by the staging above)
-        constexpr int LKS = KS == 9 ? 6 : 4;
+        constexpr int LKS = 4;
 #pragma unroll
         for (int it = 0; it < NLOAD; ++it)
           if (!LATE && it * LKS / NLOAD == ks) pf_issue(pfn, it);
@@ -522,7 +473,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
               acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                  __builtin_bit_cast(f16x8_t, fw[PB[q]][nt]), __builtin_bit_cast(f16x8_t, fa[PA[q]][mt]),
+                  __builtin_bit_cast(f16x8_t, fw[PO::PB[q]][nt]), __builtin_bit_cast(f16x8_t, fa[PO::PA[q]][mt]),
                   (ks == 0 && q == 0) ? (f32x4){0.f, 0.f, 0.f, 0.f} : acc[mt][nt], 0, 0, 0);   // (the first product starts from a zero literal)
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -534,29 +485,17 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
     auto epi_piece = [&](int i) __attribute__((always_inline)) {
       const int mt = i / NT, nt = i % NT;
       const float livef = cur_off[mt] != BX_OOB ? 1.f : 0.f;
-      f32x4 o = acc[mt][nt] * desc;
-      if (ACCUM) {
-        const float4 q = cy[ACCUM ? i : 0];
-        o += (f32x4){q.x, q.y, q.z, q.w};
-      }
-      if (EPIACT) {
-        const float4 q = XSRC == 2 ? cxw[i] : cact[EPIACT && XSRC != 2 ? i : 0];
-        o *= (f32x4){act_grad_from_out(q.x, EPIACT), act_grad_from_out(q.y, EPIACT), act_grad_from_out(q.z, EPIACT),
-                     act_grad_from_out(q.w, EPIACT)};
-      }
+      const f32x4 o = fbc_epi_value<ACCUM, EPIACT>(acc[mt][nt], desc, cy[ACCUM ? i : 0], XSRC == 2 ? cxw[i] : cact[EPIACT && XSRC != 2 ? i : 0]);
       const u32x4 ov = {__float_as_uint(o[0]), __float_as_uint(o[1]), __float_as_uint(o[2]), __float_as_uint(o[3])};
       __builtin_amdgcn_raw_buffer_store_b128(ov, bx_rsrc(cur_y, y_bytes), cur_off[mt] + nt * 64, 0, 0);
       if (EPIAB) {
         const float4 xv = XSRC == 1 ? cxw[i] : cab[EPIAB && XSRC != 1 ? i : 0];
-        const float g0 = o[0] * livef, g1 = o[1] * livef, g2 = o[2] * livef, g3 = o[3] * livef;
-        sA[nt][0] += g0, sA[nt][1] += g1, sA[nt][2] += g2, sA[nt][3] += g3;
-        sB[nt][0] = __builtin_fmaf(g0, xv.x, sB[nt][0]), sB[nt][1] = __builtin_fmaf(g1, xv.y, sB[nt][1]);
-        sB[nt][2] = __builtin_fmaf(g2, xv.z, sB[nt][2]), sB[nt][3] = __builtin_fmaf(g3, xv.w, sB[nt][3]);
+        fbc_ab_add(o, livef, xv, sA[nt], sB[nt]);
       }
       if (XSH) x_issue(n1, ty1, tx1, live1, i, i + 1);   // (the shared register is free again: the next tile's piece)
     };
 
-    // ---------------- weight gradient: this wave's 9 NA NB accumulator tiles over the 64 pixels of its tile rows 4 w .. 4 w + 3: two
+    // ---------------- weight gradient: this wave's 9 accumulator tiles over the 64 pixels of its tile rows 4 w .. 4 w + 3: two
     // k-steps of 32 pixels (tile rows 4 w + 2 s, + 1), per k-step the x^T fragments (planes) against the gy fragments of the 9 tap
     // shifts - centre pixel (r', c') meets the halo pixel (r' + 2 - ky, c' + 2 - kx), so tap row ky of k-step s reads the halo row pair
     // (4 w + 2 s + 2 - ky, + 1).  One fragment set per tap (see D); the input gradient's epilogue and the next tile's halo
@@ -569,7 +508,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
         for (int ab = 0; ab < NA; ++ab) {
           const unsigned short* xq = xt + ((hr0 + 2 * s) * FC_TC + 4 * lg + tq) * PSX + ab * 16 + tp * 4;
 #pragma unroll
-          for (int p = 0; p < NP; ++p) fx[ab][p] = fc_tr_read8(xq + p * CX, xq + FC_TC * PSX + p * CX);
+          for (int p = 0; p < NP; ++p) fx[ab][p] = fbc_tr_read8(xq + p * CX, xq + FC_TC * PSX + p * CX);
         }
       };
       // tap (ky, kx) of k-step s: halo rows row0, row0 + 1 shifted by 2 - kx columns; one fragment set per tap
@@ -579,7 +518,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
         for (int bb = 0; bb < NB; ++bb) {
           const unsigned short* gq = xh + (row0 * IC + (4 * lg + tq) + 2 - kx) * PSG + bb * 16 + tp * 4;
 #pragma unroll
-          for (int p = 0; p < NP; ++p) G[bb][p] = fc_tr_read8(gq + p * CG, gq + IC * PSG + p * CG);
+          for (int p = 0; p < NP; ++p) G[bb][p] = fbc_tr_read8(gq + p * CG, gq + IC * PSG + p * CG);
         }
 #pragma unroll
         for (int ab = 0; ab < NA; ++ab)
@@ -588,8 +527,8 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
               const int j = ((ky * 3 + kx) * NA + ab) * NB + bb;
-              accw[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, fx[ab][PA[q]]),
-                                                               __builtin_bit_cast(f16x8_t, G[bb][PB[q]]), accw[j], 0, 0, 0);
+              accw[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, fx[ab][PO::PA[q]]),
+                                                               __builtin_bit_cast(f16x8_t, G[bb][PO::PB[q]]), accw[j], 0, 0, 0);
             }
       };
       auto ride = [&](int slot) __attribute__((always_inline)) {   // slot 0 .. 5
@@ -602,7 +541,7 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
           if (LATE && 4 + it * 2 / NLOAD == slot) pf_issue(pfn, it);          // ... or are requested now, behind the epilogue
         }
       };
-      fc_static_for<0, 6>([&](auto sc_) __attribute__((always_inline)) {
+      fbc_static_for<0, 6>([&](auto sc_) __attribute__((always_inline)) {
         constexpr int slot = decltype(sc_)::value, s = slot / 3, ky = slot % 3;
         if (ky == 0) load_x(s);
         ride(slot);
@@ -671,8 +610,8 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
         need = true;
         break;
       }
-      if (!s_set && adds) {   // the first tile with something to add sets the exponent, FC_SMARGIN bits of headroom
-        S_w = ex_e + sx_e - FC_SMARGIN;
+      if (!s_set && adds) {   // the first tile with something to add sets the exponent, FBC_SMARGIN bits of headroom
+        S_w = ex_e + sx_e - FBC_SMARGIN;
         s_set = true;
       }
       rest();
@@ -706,57 +645,16 @@ __global__ __launch_bounds__(256, (FcCfg<CG, CX>::WPC)) void conv_bwd_fused_c16_
   }
 }
 
-int dis_fc_wpc(int cg, int cx) {
-  if (cg == 16 && cx == 16) return FcCfg<16, 16>::WPC;
-  return 0;
-}
+int dis_fc_wpc(int cg, int cx) { return (cg == FcCfg::CG && cx == FcCfg::CX) ? FcCfg::WPC : 0; }
 
-// Launch: hipErrorInvalidValue when no instance exists for the combination (the caller keeps the two launches).
-template <int CG, int CX>
-static hipError_t fc_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream) {
-  using K = FcCfg<CG, CX>;
-  const ConvArgs& a = f.c;
-  static bool attr_set[16] = {};
-  auto launch = [&](auto kern, int slot) -> hipError_t {
-    if (!attr_set[slot]) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES);
-      if (e != hipSuccess) return e;
-      attr_set[slot] = true;
-    }
-    DIS_TAG("conv_bwd_c16_fused_kernel<16,16>");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(K::NTHR), K::LDS_BYTES, stream, f);
-    return hipSuccess;
-  };
-  constexpr int S = DIS_ACT_SELU;
-  if (inact != 0 && inact != S) return hipErrorInvalidValue;
-  const bool coef = a.gnb_coef != nullptr, gst = a.gnb_out != nullptr, ab = a.ab_out != nullptr, epiact = a.ab_act_y != nullptr;
-  if (!coef) {
-    // plain operand (gy itself, or gy act'(y)): no epilogue forms
-    if (ab || gst || xgn || xsrc) return hipErrorInvalidValue;
-    if (a.accum) return inact ? launch(conv_bwd_fused_c16_kernel<CG, CX, S, false, true, false, 0, 0, false, false>, 0)
-                              : launch(conv_bwd_fused_c16_kernel<CG, CX, 0, false, true, false, 0, 0, false, false>, 1);
-    return inact ? launch(conv_bwd_fused_c16_kernel<CG, CX, S, false, false, false, 0, 0, false, false>, 2)
-                 : launch(conv_bwd_fused_c16_kernel<CG, CX, 0, false, false, false, 0, 0, false, false>, 3);
-  }
-  if constexpr (CG == CX) {
-    if (ab && !a.accum && !epiact && xsrc == 1 && xgn) {   // conv2d_gn_in: the GroupNorm input of the sums is the conv's input
-      if (gst) return inact ? hipErrorInvalidValue : launch(conv_bwd_fused_c16_kernel<CG, CX, 0, true, false, true, 0, 1, true, true>, 4);
-      return inact ? launch(conv_bwd_fused_c16_kernel<CG, CX, S, true, false, true, 0, 1, true, false>, 5)
-                   : launch(conv_bwd_fused_c16_kernel<CG, CX, 0, true, false, true, 0, 1, true, false>, 6);
-    }
-    if (gst || xgn) return hipErrorInvalidValue;
-    if (ab && a.accum && epiact && xsrc == 2 && inact == S)   // ResNetBlock chain: x = SELU(GroupNorm(x2) + res) is the conv's input
-      return launch(conv_bwd_fused_c16_kernel<CG, CX, S, true, true, true, S, 2, false, false>, 7);
-    if (ab && a.accum && !epiact && xsrc == 0 && inact == S)  // two-consumer GroupNorm output
-      return launch(conv_bwd_fused_c16_kernel<CG, CX, S, true, true, true, 0, 0, false, false>, 8);
-    if (!ab && a.accum && xsrc == 0 && inact == S) return launch(conv_bwd_fused_c16_kernel<CG, CX, S, true, true, false, 0, 0, false, false>, 9);
-    if (!ab && !a.accum && xsrc == 0)
-      return inact ? launch(conv_bwd_fused_c16_kernel<CG, CX, S, true, false, false, 0, 0, false, false>, 10)
-                   : launch(conv_bwd_fused_c16_kernel<CG, CX, 0, true, false, false, 0, 0, false, false>, 11);
-  }
-  return hipErrorInvalidValue;
-}
-hipError_t dis_fc_launch(const FbArgs& f, int cg, int cx, int inact, bool xgn, int xsrc, long grid, hipStream_t stream) {
-  if (cg == 16 && cx == 16) return fc_launch<16, 16>(f, inact, xgn, xsrc, grid, stream);
-  return hipErrorInvalidValue;
+// Launch (f.c.cx channels of gy, f.c.cy of x): hipErrorInvalidValue when no instance exists for the combination (the caller keeps the
+// two launches).
+hipError_t dis_fc_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream) {
+  if (dis_fc_wpc(f.c.cx, f.c.cy) <= 0) return hipErrorInvalidValue;
+  static bool attr_set[FBC_NFORMS] = {};
+  return fbc_dispatch(f.c, inact, xgn, xsrc, [&](auto form) {
+    using F = decltype(form);
+    return fbc_launch<FcCfg>(conv_bwd_fused_c16_kernel<F::INACT, F::INCOEF, F::ACCUM, F::EPIAB, F::EPIACT, F::XSRC, F::XGN, F::GST>,
+                             attr_set[F::SLOT], "conv_bwd_c16_fused_kernel<16,16>", f, grid, stream);
+  });
 }
