@@ -2270,9 +2270,10 @@ extern "C" long dis_conv2d_bwd_fused_workspace(int c) {
   return wgrad_ws<32, 32, 3, 3, 1>();
 }
 
-// The one host path of the three one-launch kernels (two-term 32 -> 32 and 16 -> 16, three-term 32 -> 32).  What a family is:
+// The one host path of the one-launch kernels (two-term 32 -> 32, 16 -> 16 and the mixed pairs, three-term 32 -> 32).  What a family is:
 struct BwdFusedFamily {
-  int c;            // the channel count it accepts on both sides
+  int c;            // the channel count it accepts for x / gx (the conv's input) ...
+  int cg;           // ... and for g (the conv's output): c, or the other of 16 / 32 for a mixed pair
   int wpc;          // workgroups per CU: the grid is at most wpc x #CUs (<= 0: no kernel)
   int tile_rows;    // rows of a tile (16 columns)
   bool forms;       // the coef operand, the gpre store and the channel sums exist (gnb_*, ab_*); otherwise they arrive null
@@ -2282,7 +2283,7 @@ struct BwdFusedFamily {
   hipError_t (*launch)(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
 };
 // Checks (their order is the precedence of the error codes), FbArgs, grid, workspace split, launch, slab reduce.  The slab a workgroup
-// leaves is [tap * c + ci][co] (one chunk of c channels, no tap-row split: WgCfg<32, 32, 3, 3, 1>'s layout at c = 32) and the
+// leaves is [tap * c + ci][co] with cg columns (one chunk of c channels, no tap-row split: WgCfg<32, 32, 3, 3, 1>'s layout at c = 32) and the
 // workspace wgrad_ws's: WG_WORKERS slabs, the unused level-1 scratch, the bias partials.
 static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float* q, const float* coef, int in_act, float* gpre_out,
                          const float* w_oihw, int w_o, int w_i, int w_row_stride, float* gx, int accumulate, const float* ab_gn_x,
@@ -2291,11 +2292,13 @@ static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float*
                          float* workspace, int n, int hin, int win, int c, int grad_w_row_stride, void* stream) {
   if (!g || !w_oihw || !gx || !x || !grad_w || !workspace) return DIS_ERR_NULL;
   if (n <= 0 || hin <= 0 || win <= 0) return DIS_ERR_BAD_SHAPE;
-  if (fam.wpc <= 0 || c != fam.c || w_o != c || w_i != c) return DIS_ERR_UNSUPPORTED;
+  if (fam.wpc <= 0 || c != fam.c || w_o != fam.cg || w_i != c) return DIS_ERR_UNSUPPORTED;
+  const int cg = fam.cg;
   if (in_act != DIS_ACT_NONE && in_act != DIS_ACT_SELU) return DIS_ERR_UNSUPPORTED;
   if ((coef || in_act) && !q) return DIS_ERR_NULL;
   if (gpre_out && !coef) return DIS_ERR_BAD_SHAPE;
-  if ((ab_out != nullptr) != (ab_gn_x != nullptr) || (ab_act_y && (!ab_out || !accumulate))) return DIS_ERR_BAD_SHAPE;
+  if ((ab_out != nullptr) != (ab_gn_x != nullptr) || (ab_act_y && (!ab_out || (!accumulate && cg == c))))
+    return DIS_ERR_BAD_SHAPE;   // (a mixed pair has the written form: dis_conv2d_dgrad_bf16x3_act_gnsums_res's)
   if (fam.own_slots && ab_out && ab_slots < 1) return DIS_ERR_BAD_SHAPE;
   if (x_gn_stats && (!x_gn_gamma || !x_gn_beta)) return DIS_ERR_NULL;
   if (w_row_stride == 0) w_row_stride = w_i * 9;
@@ -2306,7 +2309,7 @@ static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float*
   if (grad_w_row_stride < c * 9 || grad_w_row_stride % 9) return DIS_ERR_BAD_SHAPE;
   static const bool off = getenv("DIS_BWD_FUSED") && getenv("DIS_BWD_FUSED")[0] == '0';
   if (off || dis_f2_enabled() != fam.f2) return DIS_ERR_UNSUPPORTED;
-  if ((long)hin * win * c * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
+  if ((long)hin * win * (c > cg ? c : cg) * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
   FbArgs f;
   ConvArgs& a = f.c;
   a.x = g; a.w = w_oihw; a.bias = nullptr; a.y = gx; a.stats = nullptr;
@@ -2316,7 +2319,7 @@ static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float*
   a.xscale = nullptr; a.yscale = nullptr;
   a.wmode = 1; a.w_o = w_o; a.w_i = w_i; a.w_rs = w_row_stride;
   a.xact = q;
-  a.ldx = a.ldy = c; a.cx = a.cy = c; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
+  a.ldx = a.cx = cg; a.ldy = a.cy = c; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
   a.gn_stats = nullptr; a.gn_gamma = nullptr; a.gn_beta = nullptr; a.gn_eps = 0.f;
   a.ab_x = ab_gn_x; a.ab_out = ab_out; a.ab_slots = !fam.forms ? 0 : (fam.own_slots ? ab_slots : num_cus()); a.ab_act_y = ab_act_y;
   a.gnb_coef = coef; a.gnb_out = gpre_out; a.gnb_act = 0;
@@ -2331,7 +2334,7 @@ static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float*
   if (grid > ntiles) grid = ntiles;
   if (grid >= 8) grid -= grid % 8;   // (a multiple of 8 is dealt evenly to the XCDs: fbc_tile_share)
   if (grid < 1) grid = 1;
-  const long elems = 9L * c * c;
+  const long elems = 9L * c * cg;
   f.part = workspace;
   f.bpart = grad_b ? workspace + (long)WG_WORKERS * elems + (long)WG_RSPLIT * elems : nullptr;
   hipStream_t s = (hipStream_t)stream;
@@ -2340,9 +2343,9 @@ static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float*
   if (le != hipSuccess) return (int)le;
   // (cin_real = the row pitch of grad_w in input channels; the last argument: the second float of every bias partial)
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_grid(elems, grad_b != nullptr)), dim3(64 * WG_RW), 0, s,
-                     (const float*)f.part, grad_w, c, 1, 1, 3, 3, 3, c, grad_w_row_stride / 9, (int)elems,
+                     (const float*)f.part, grad_w, c, 1, 1, 3, 3, 3, cg, grad_w_row_stride / 9, (int)elems,
                      (const float*)(grad_b ? f.bpart : nullptr), grad_b, (int)grid,
-                     (const float*)(grad_b && fam.bias_floats == 2 ? f.bpart + grid * c : nullptr));
+                     (const float*)(grad_b && fam.bias_floats == 2 ? f.bpart + grid * cg : nullptr));
   DIS_CHECK_LAUNCH();
   return DIS_OK;
 }
@@ -2356,7 +2359,7 @@ extern "C" int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const 
                                           const double* x_gn_stats, const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps,
                                           float* grad_w, float* grad_b, float* workspace, int n, int hin, int win, int c,
                                           int grad_w_row_stride, void* stream) {
-  static const BwdFusedFamily fam = {/*c*/ 32, /*wpc*/ 1, /*tile_rows*/ 16, /*forms*/ true, /*own_slots*/ false, /*bias_floats*/ 1,
+  static const BwdFusedFamily fam = {/*c*/ 32, /*cg*/ 32, /*wpc*/ 1, /*tile_rows*/ 16, /*forms*/ true, /*own_slots*/ false, /*bias_floats*/ 1,
                                      /*f2*/ true, dis_fb_launch};
   return bwd_fused_run(fam, g, q, coef, in_act, gpre_out, w_oihw, w_o, w_i, w_row_stride, gx, accumulate, ab_gn_x, ab_act_y, ab_out, 0, x,
                        x_gn_stats, x_gn_gamma, x_gn_beta, x_gn_eps, grad_w, grad_b, workspace, n, hin, win, c, grad_w_row_stride, stream);
@@ -2400,21 +2403,24 @@ extern "C" int dis_conv2d_bwd1x1_scaled_gnb(const float* g, const float* q, cons
   return DIS_OK;
 }
 
-/* The same ONE launch for the 3x3 stride-1 pad-1 layers with 16 channels on a side (conv_bwd_fused_c16.hip): cout = w_o channels of
- * g / q / gpre_out, cin = w_i channels of x / gx / ab_gn_x / ab_act_y.  Forms and results as above.  The kernel runs up to
- * dis_conv2d_bwd_fused_c16_slots() workgroups (two per CU for 16 -> 16); one with channel sums runs ab_slots at most - the slots the
- * caller allocated per sample of ab_out and hands to dis_gn_bwd_coef. */
+/* The same ONE launch for the 3x3 stride-1 pad-1 layers with 16 channels on a side (conv_bwd_fused_c16.hip for 16 -> 16,
+ * conv_bwd_fused_mixed.hip for 16 -> 32 and 32 -> 16): cout = w_o channels of g / q / gpre_out, cin = w_i channels of x / gx /
+ * ab_gn_x / ab_act_y.  Forms and results as above; a mixed pair has the operand g act'(q), not accumulating, with the plain epilogue
+ * or with ab_act_y == x, ab_gn_x and ab_out (gx = conv_T(.) selu'(x) WRITTEN, plus the sums: dis_conv2d_dgrad_bf16x3_act_gnsums_res's
+ * arithmetic).  The kernel runs up to dis_conv2d_bwd_fused_c16_slots() workgroups (two per CU for 16 -> 16, one for a mixed pair); one
+ * with channel sums runs ab_slots at most - the slots the caller allocated per sample of ab_out and hands to dis_gn_bwd_coef. */
+static int fc_wpc(int cg, int cx) { return cg == cx ? dis_fc_wpc(cg, cx) : dis_fm_wpc(cg, cx); }
 static long fc_max_grid(int cin, int cout) {
-  long g = (long)dis_fc_wpc(cout, cin) * num_cus();
+  long g = (long)fc_wpc(cout, cin) * num_cus();
   return g > WG_WORKERS ? WG_WORKERS : g;
 }
 extern "C" long dis_conv2d_bwd_fused_c16_workspace(int cin, int cout) {
-  if (dis_fc_wpc(cout, cin) <= 0) return -1;
+  if (fc_wpc(cout, cin) <= 0) return -1;
   const long elems = 9L * cin * cout;   // (wgrad_ws's layout: slabs, the unused level-1 scratch, bias partials)
   return (long)WG_WORKERS * elems + (long)WG_RSPLIT * elems + 2L * WG_WORKERS * cout;   // (two floats per bias partial)
 }
 extern "C" long dis_conv2d_bwd_fused_c16_slots(int cin, int cout) {
-  return dis_fc_wpc(cout, cin) <= 0 ? -1 : fc_max_grid(cin, cout);
+  return fc_wpc(cout, cin) <= 0 ? -1 : fc_max_grid(cin, cout);
 }
 extern "C" int dis_conv2d_bwd_fused_f16x2_c16(const float* g, const float* q, const float* coef, int in_act, float* gpre_out,
                                               const float* w_oihw, int w_o, int w_i, int w_row_stride, float* gx, int accumulate,
@@ -2422,9 +2428,11 @@ extern "C" int dis_conv2d_bwd_fused_f16x2_c16(const float* g, const float* q, co
                                               const float* x, const double* x_gn_stats, const float* x_gn_gamma,
                                               const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b, float* workspace,
                                               int n, int hin, int win, int grad_w_row_stride, void* stream) {
-  // (a pair without a kernel - dis_fc_wpc 0 - is DIS_ERR_UNSUPPORTED; the kernel keeps fp64 bias sums: two floats per partial)
-  const BwdFusedFamily fam = {/*c*/ 16, /*wpc*/ dis_fc_wpc(w_o, w_i), /*tile_rows*/ 16, /*forms*/ true, /*own_slots*/ true,
-                              /*bias_floats*/ 2, /*f2*/ true, dis_fc_launch};
+  // (a pair without a kernel - fc_wpc 0 - is DIS_ERR_UNSUPPORTED; the kernels keep fp64 bias sums: two floats per partial)
+  const int wpc = fc_wpc(w_o, w_i);
+  const bool mixed = wpc > 0 && w_o != w_i;
+  const BwdFusedFamily fam = {/*c*/ mixed ? w_i : 16, /*cg*/ mixed ? w_o : 16, wpc, /*tile_rows*/ 16, /*forms*/ true, /*own_slots*/ true,
+                              /*bias_floats*/ 2, /*f2*/ true, mixed ? dis_fm_launch : dis_fc_launch};
   return bwd_fused_run(fam, g, q, coef, in_act, gpre_out, w_oihw, w_o, w_i, w_row_stride, gx, accumulate, ab_gn_x, ab_act_y, ab_out,
                        ab_slots, x, x_gn_stats, x_gn_gamma, x_gn_beta, x_gn_eps, grad_w, grad_b, workspace, n, hin, win, fam.c,
                        grad_w_row_stride, stream);
@@ -2443,7 +2451,7 @@ extern "C" int dis_conv2d_bwd_fused_bf16x3(const float* g, const float* q, int i
                                            const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w,
                                            float* grad_b, float* workspace, int n, int hin, int win, int c, int grad_w_row_stride,
                                            void* stream) {
-  static const BwdFusedFamily fam = {/*c*/ 32, /*wpc*/ 1, /*tile_rows*/ 8, /*forms*/ false, /*own_slots*/ false, /*bias_floats*/ 1,
+  static const BwdFusedFamily fam = {/*c*/ 32, /*cg*/ 32, /*wpc*/ 1, /*tile_rows*/ 8, /*forms*/ false, /*own_slots*/ false, /*bias_floats*/ 1,
                                      /*f2*/ false, dis_fb3_launch};
   return bwd_fused_run(fam, g, q, nullptr, in_act, nullptr, w_oihw, w_o, w_i, w_row_stride, gx, accumulate, nullptr, nullptr, nullptr, 0, x,
                        x_gn_stats, x_gn_gamma, x_gn_beta, x_gn_eps, grad_w, grad_b, workspace, n, hin, win, c, grad_w_row_stride, stream);

@@ -104,6 +104,10 @@ hipError_t dis_fb_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long gr
 // for (0: no kernel)
 hipError_t dis_fc_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
 int dis_fc_wpc(int cg, int cx);
+// conv_bwd_fused_mixed.hip: the same for the pairs (cg, cx) = (32, 16) and (16, 32) (part: slabs of 9 * cx * cg floats, element
+// [(tap * cx + ci) * cg + co]; bpart: [workgroup][cg] sums followed by [workgroup][cg] remainders)
+hipError_t dis_fm_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
+int dis_fm_wpc(int cg, int cx);
 // conv_bwd_fused_bf16x3.hip: the same with three-term bf16 operands (plain / act / GroupNorm(x) forms; c.gnb_* and c.ab_* unused, xsrc 0)
 hipError_t dis_fb3_launch(const FbArgs& f, int inact, bool xgn, int xsrc, long grid, hipStream_t stream);
 

@@ -1,5 +1,6 @@
 // Shared parts of the one-launch 3x3 conv backward kernels - conv_bwd_fused.hip (32 -> 32, two-term fp16), conv_bwd_fused_c16.hip
-// (16 -> 16, two-term fp16) and conv_bwd_fused_bf16x3.hip (32 -> 32, three-term bf16); included by these three files only.
+// (16 -> 16, two-term fp16), conv_bwd_fused_mixed.hip (16 <-> 32, two-term fp16) and conv_bwd_fused_bf16x3.hip (32 -> 32, three-term
+// bf16); included by these four files only.
 // What is here is a pure function of its arguments: the small device helpers, the walk over the tiles, the table that maps a call's
 // form to a kernel instance, and the launch helper.  The phases of the kernels themselves stay in their files: the 32 -> 32 two-term
 // kernel fills the register file, and moving its text moves its registers (profiles/r9_bwd_fused_shared.md).

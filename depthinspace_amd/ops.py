@@ -1235,7 +1235,8 @@ def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=
                times act'(y) on load when act != ACT_NONE (the bf16x3 shapes) and as the pre-activation gradient otherwise
       x: the conv's input; xgn = (stats, gamma, beta, eps): the conv stages GroupNorm(x) (conv2d_gn_in)
       gx: input-gradient target (None: not wanted), accumulate: add to what it holds; sums = (ab_x, ab_act): its launch also leaves
-          the GroupNorm-backward channel sums of ab_x - without xgn for the GroupNorm that produced x (_GN_PRE)
+          the GroupNorm-backward channel sums of ab_x - without xgn for the GroupNorm that produced x (_GN_PRE).  With an activation
+          operand (16 <-> 32, ab_act is x, not accumulating) gx is WRITTEN times act'(x): final_conv, ref_conv's 16-channel source
       grads = (gw, gb): the weight / bias gradient targets (gw may be a slice of a wider gradient); None: the sinks of weight / bias
       keep_gpre: the operand formed from a token is stored for the caller (conv2d_multi's other sources read it)
       after_dgrad(ab, slots): runs once the input gradient is written, before the weight gradient (the GroupNorm backward of xgn)
@@ -1244,19 +1245,24 @@ def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=
     n, h, w, cin_pad = x.shape
     split = lib.fn('dis_get_conv_split')() == 1
     epi = gx is not None and sums is not None and split and act == ACT_NONE and cin == cout and _bx_shape(cin, cout, k, 1)
+    # the same sums behind an activation operand (dis_conv2d_dgrad_bf16x3_act_gnsums_res's form)
+    epi_act = (gx is not None and sums is not None and split and act == ACT_SELU and lz is None and xgn is None and not accumulate and
+               (cin, cout) in ((16, 32), (32, 16)) and sums[1] is x and cin_pad == cin and (k, pad) == (3, 1) and _bx_shape(cin, cout, k, 1))
     if lz is not None and not (gx is not None and split and act == ACT_NONE and cin_pad == cin and
                                _gn_lazy_shape(cin, cout, k, 1, pad) and (xgn is None or epi)):
         gy, lz = _gn_lazy_materialize(lz), None
     # one launch for both gradients (csrc/conv_bwd_fused.hip, 32 -> 32): it forms a token's operand (and stores it only in the
     # GroupNorm-on-load form) or takes gy (no epilogue then)
     # (csrc/conv_bwd_fused_c16.hip: the layers with 16 channels on a side, through an entry point of their own - its workspace
-    #  function answers -1 for a pair of channel counts without a kernel; a padded input keeps the two launches.  Only a token's
-    #  forms go there: a plain gy keeps the stand-alone weight-gradient kernel, whose sums conv2d_gn_in's backward - which has no
-    #  one-launch form - reproduces BIT for bit at 16 channels (tests/test_net_ops_gpu.py holds the pair to that))
+    #  function answers -1 for a pair of channel counts without a kernel; a padded input keeps the two launches.  At 16 -> 16 only a
+    #  token's forms go there: a plain gy keeps the stand-alone weight-gradient kernel, whose sums conv2d_gn_in's backward - which has
+    #  no one-launch form - reproduces BIT for bit at 16 channels (tests/test_net_ops_gpu.py holds the pair to that).  The mixed pairs
+    #  (csrc/conv_bwd_fused_mixed.hip) have the activation operand, written, with or without the sums)
     c16 = (cin, cout) != (32, 32)
+    mixed_act = cin != cout and act == ACT_SELU and not accumulate and (sums is None or epi_act)
     fused = (gx is not None and split and BWD_FUSED and BF16X3 and cin in (16, 32) and cout in (16, 32) and cin_pad == cin and
              (k, pad) == (3, 1) and ((not keep_gpre or xgn is not None) if lz is not None else
-                                     (sums is None and xgn is None and not c16)))
+                                     (xgn is None and (mixed_act if c16 else sums is None))))
     fkey = (cin, cout) if c16 else cin
     if fused and fkey not in _FUSED_WS:
         _FUSED_WS[fkey] = (lib.fn('dis_conv2d_bwd_fused_c16_workspace')(cin, cout) if c16 else
@@ -1265,8 +1271,8 @@ def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=
             _FUSED_WS['slots', cin, cout] = lib.fn('dis_conv2d_bwd_fused_c16_slots')(cin, cout)
     fused = fused and _FUSED_WS[fkey] >= 0
     # (the 16 -> 16 kernel runs two workgroups per CU: one slot of channel sums per workgroup)
-    ab, slots = _gn_sums(n, cin, x.device, _FUSED_WS['slots', cin, cout] if fused and c16 else None) if epi else (None, 0)
-    ab_x, ab_act = sums if epi else (None, None)
+    ab, slots = _gn_sums(n, cin, x.device, _FUSED_WS['slots', cin, cout] if fused and c16 else None) if epi or epi_act else (None, 0)
+    ab_x, ab_act = sums if epi or epi_act else (None, None)
     acc = 1 if accumulate else 0
 
     def dgrad_done():
@@ -1324,7 +1330,9 @@ def _conv_bwd_slice(weight, x, gx, accumulate, grads=None, bias=None, pad=1, lz=
         after = dgrad_done()
     elif gx is not None:
         kw = (n, gy.shape[1], gy.shape[2], cout, cin, k - 1 - pad)
-        if act != ACT_NONE:
+        if act != ACT_NONE and ab is not None:
+            lib.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gy, y, weight, cout, cin, weight.stride(0), gx, ab_act, ab_x, ab, *kw)
+        elif act != ACT_NONE:
             lib.call('dis_conv2d_dgrad_bf16x3_act', gy, y, act, weight, cout, cin, weight.stride(0), gx, *kw, acc)
         elif ab is not None and accumulate:
             lib.call('dis_conv2d_dgrad_bf16x3_gnsums_res', gy, weight, cout, cin, weight.stride(0), gx, ab_act, ab_x, ab, *kw)
@@ -1454,22 +1462,17 @@ class _Conv2d(torch.autograd.Function):
             _sinks_written()
             return gx, gw_ret, gb_ret, None, None, None, None, None, None, None, None, None
         gnres = ctx.gnres
+        sums = None
         if (want_gx and fuse_act and gnres is not None and ctx.join is None and act == ACT_SELU and (GN_SUMS & 1) and
                 (cout, cin) == (16, 32) and tuple(gnres[0].shape) == tuple(x.shape) and lib.fn('dis_get_conv_split')() == 1):
-            # final_conv: x = SELU(GroupNorm(.) + res) of ref_res3 and this conv is its only consumer - its input-gradient launch
-            # leaves that GroupNorm's backward sums (as the residual form below)
-            gx = torch.empty_like(x)
-            ab, slots = _gn_sums(n, cin, x.device)
-            lib.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gy, y, weight, cout, cin, weight.stride(0), gx, x, gnres[0], ab,
-                     n, gy.shape[1], gy.shape[2], cout, cin, k - 1 - pad)
-            _GN_PRE[gx.data_ptr()] = (ab, slots)
-            want_gx = False
+            # final_conv: x = SELU(GroupNorm(.) + res) of ref_res3 and this conv is its only consumer - its input gradient is written
+            # times SELU'(x) and its launch leaves that GroupNorm's backward sums (as the residual form below)
+            sums = (gnres[0], x)
         tgt, second = join.target(x) if want_gx else (None, False)
         # x is out = SELU(GroupNorm(x2) + res) of the previous ResNetBlock (gnres = (x2,)), or GroupNorm(x2) with two consumers
         # (gnres = (x2, None)), and gx - which arrives holding the other consumer's gradient - becomes the complete gradient wrt out
         # here: the epilogue turns it into the gradient wrt the pre-activation value (times SELU'(x)) and leaves the
         # GroupNorm-backward sums, so that GroupNorm's backward needs neither its reduce pass nor a residual-gradient write
-        sums = None
         if second and gnres is not None and (GN_SUMS & 2) and tuple(gnres[0].shape) == tuple(x.shape):
             sums = (gnres[0], x if len(gnres) == 1 else None)
         _, gw_ret, gb_ret, _ = _conv_bwd_slice(weight, x, tgt, second, bias=ctx.bias_ref, pad=pad, lz=lz, gy=gy if fuse_act else gpre,
@@ -1703,11 +1706,7 @@ class _Conv2dMulti(torch.autograd.Function):
             elif (gx is not None and fuse_act and act == ACT_SELU and gnres is not None and (GN_SUMS & 1) and (cout, cs[i]) == (32, 16) and
                   k == 3 and pad == 1 and tuple(gnres[0].shape) == tuple(x.shape) and lib.fn('dis_get_conv_split')() == 1):
                 # (x = SELU(GroupNorm(.) + res) of a ResNetBlock and this slice is its only consumer: as final_conv in _Conv2d.backward)
-                ab, slots = _gn_sums(n, cs[i], x.device)
-                lib.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gy, y, wi, cout, cs[i], wi.stride(0), gx, x, gnres[0], ab,
-                         n, gy.shape[1], gy.shape[2], cout, cs[i], k - 1 - pad)
-                _GN_PRE[gx.data_ptr()] = (ab, slots)
-                _conv_bwd_slice(wi, x, None, False, grads, pad=pad, gy=gy, act=act, y=y)
+                _conv_bwd_slice(wi, x, gx, False, grads, pad=pad, gy=gy, act=act, y=y, sums=(gnres[0], x))
             else:
                 gpre_i = _conv_bwd_slice(wi, x, gx, False, grads, pad=pad, lz=lz, gy=gy if fuse_act else gpre,
                                          act=act if fuse_act else ACT_NONE, y=y, keep_gpre=True)[0]

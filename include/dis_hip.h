@@ -455,10 +455,14 @@ int dis_conv2d_bwd_fused_f16x2(const float* g, const float* q, const float* coef
                                const float* ab_act_y, double* ab_out, const float* x, const double* x_gn_stats,
                                const float* x_gn_gamma, const float* x_gn_beta, float x_gn_eps, float* grad_w, float* grad_b,
                                float* workspace, int n, int hin, int win, int c, int grad_w_row_stride, void* stream);
-/* The same ONE launch for the 3x3 stride-1 pad-1 layers with 16 channels on a side (csrc/conv_bwd_fused_c16.hip): w_oihw is
+/* The same ONE launch for the 3x3 stride-1 pad-1 layers with 16 channels on a side (csrc/conv_bwd_fused_c16.hip for 16 -> 16,
+ * csrc/conv_bwd_fused_mixed.hip for 16 -> 32 and 32 -> 16): w_oihw is
  * (w_o, w_i, 3, 3), g / q / gpre_out have w_o channels, x / gx / ab_gn_x / ab_act_y w_i.  Operand, input-gradient forms (gx BIT-identical
  * to the two launches'), x / x_gn_*, grad_w (rows grad_w_row_stride floats apart, 0 = contiguous) and grad_b (w_o) as
- * dis_conv2d_bwd_fused_f16x2.  The kernel runs dis_conv2d_bwd_fused_c16_slots(w_i, w_o) workgroups at most (two per CU for 16 -> 16):
+ * dis_conv2d_bwd_fused_f16x2.  A mixed pair has two forms, both with the operand g selu'(q) (coef NULL, in_act SELU) and
+ * accumulate == 0: all of ab_* NULL (gx = conv_T(.)), or ab_act_y == x with ab_gn_x and ab_out (gx = conv_T(.) selu'(x), WRITTEN, and
+ * the channel sums of gx and gx ab_gn_x: dis_conv2d_dgrad_bf16x3_act_gnsums_res's arithmetic).
+ * The kernel runs dis_conv2d_bwd_fused_c16_slots(w_i, w_o) workgroups at most (two per CU for 16 -> 16, one for a mixed pair):
  *   workspace: dis_conv2d_bwd_fused_c16_workspace(w_i, w_o) floats (-1: no kernel for this pair of channel counts);
  *   ab_out: (n, ab_slots, 2, w_i) doubles, ZEROED by the caller, one slot per workgroup - ab_slots is the caller's slot count (what it
  *     hands to dis_gn_bwd_coef); a launch with channel sums runs min(ab_slots, dis_conv2d_bwd_fused_c16_slots()) workgroups.

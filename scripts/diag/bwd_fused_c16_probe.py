@@ -39,6 +39,9 @@ def main():
         'plain_accum': (False, 0, True, None, None, x, False),
         'plain_act': (False, S, False, None, None, x, False),
     }
+    if cin != cout:
+        # final_conv / ref_conv's 16-channel source: gx = conv_T(gy selu'(y)) selu'(x) written, plus the channel sums (x fetched once)
+        forms['act_sums_res'] = (False, S, False, ab_other, xs, xs, False)
     if cin == cout:
         gamma = (torch.rand(cout, generator=g_) + 0.5).cuda()
         forms.update({
@@ -77,6 +80,10 @@ def main():
                 L.call('dis_conv2d_dgrad_f16x2_gnb', gq, q, coef, in_act, gpre, wt, cout, cin, wt.stride(0), gx, acc, ab_x, act_y, ab_old,
                        n, h, w, cin)
                 gp = gpre
+            elif in_act and ab_x is not None:
+                L.call('dis_conv2d_dgrad_bf16x3_act_gnsums_res', gq, q, wt, cout, cin, wt.stride(0), gx, act_y, ab_x, ab_old, n, h, w,
+                       cout, cin, 1)
+                gp = None
             elif in_act:
                 L.call('dis_conv2d_dgrad_bf16x3_act', gq, q, in_act, wt, cout, cin, wt.stride(0), gx, n, h, w, cout, cin, 1, acc)
                 gp = None
