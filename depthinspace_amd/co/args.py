@@ -32,6 +32,15 @@ def get_parser():
     # (not in the reference) backward of the geometric loss: float atomics, or order-free sums that repeat bit for bit
     parser.add_argument('--geo_bwd', help='Backward of the geometric loss; default: the DIS_GEO_BWD environment variable, else atomic',
                         default=None, choices=['atomic', 'det'], type=str)
+    # (not in the reference) the optimiser: the reference hard-codes Adam(lr=1e-4) and passes no scheduler (train_val.py:55-58)
+    parser.add_argument('--lr', help='Learning rate (not in the reference)', default=1e-4, type=float)
+    parser.add_argument('--lr_step', help='Multiply the learning rate by --lr_gamma every this many epochs; 0: constant '
+                        '(not in the reference)', default=0, type=int)
+    parser.add_argument('--lr_gamma', help='Factor of --lr_step (not in the reference)', default=0.5, type=float)
+    parser.add_argument('--max_grad_norm', help='Clip the gradient to this global L2 norm; default: no clipping '
+                        '(not in the reference)', default=None, type=float)
+    parser.add_argument('--skip_nonfinite', help='Skip a step whose gradient norm is inf / NaN (not in the reference)',
+                        default=False, type=str2bool)
     return parser
 
 

@@ -370,8 +370,11 @@ class Worker(object):
             mean_loss = stacked if mean_loss is None else mean_loss + stacked
             n_done += 1
             if (epoch <= 1 and batch_idx < 128) or batch_idx % 16 == 0:
+                clip = ''
+                if getattr(optimizer, 'mode', 0):   # clipping / skipping on: the device's own figures, read where the loss is
+                    clip = f' grad_norm={optimizer.last_grad_norm:.4g} skipped={optimizer.skipped_steps}'
                 logging.info(f'train e{epoch}: {batch_idx + 1}/{len(train_loader)}: '
-                             f'loss={self.format_err_str([float(e) for e in stacked.cpu()])}')
+                             f'loss={self.format_err_str([float(e) for e in stacked.cpu()])}{clip}')
         if 'cuda' in str(self.train_device):
             torch.cuda.synchronize()
         stopwatch.stop('total')
@@ -486,6 +489,8 @@ class Worker(object):
                     raise RuntimeError(f'cannot restore the optimizer from {state_path} ({type(e).__name__}: {e}); '
                                        f'set DIS_ALLOW_OPTIMIZER_RESET=1 to resume with a fresh optimizer') from e
                 logging.error(f'cannot load optimizer from state_dict ({e}): resuming with a FRESH optimizer')
+            if scheduler is not None and 'scheduler' in state and hasattr(scheduler, 'load_state_dict'):
+                scheduler.load_state_dict(state['scheduler'])
             if 'cpu_rng_state' in state:
                 torch.set_rng_state(state['cpu_rng_state'])
             if 'gpu_rng_state' in state and torch.cuda.is_available():
@@ -503,10 +508,16 @@ class Worker(object):
             self.callback_train_new_epoch(epoch, net, optimizer)
             self.train_epoch(epoch, net, optimizer, train_set)
             errs = self.test(epoch, net, test_sets)
+            # (the reference steps the scheduler after the checkpoint, :404-405, and does not save it.  Here it is saved, and a
+            # resumed run starts at epoch + 1: the checkpoint has to hold the learning rate and scheduler state of THAT epoch)
+            if scheduler is not None:
+                scheduler.step()
             if (epoch + 1) % self.save_frequency == 0 and self.is_main:
                 state_dict = {'epoch': epoch, 'min_err': min_err, 'state_dict': net.state_dict(),
                               'optimizer': optimizer.state_dict(), 'cpu_rng_state': torch.get_rng_state(),
                               'gpu_rng_state': torch.cuda.get_rng_state()}
+                if scheduler is not None and hasattr(scheduler, 'state_dict'):
+                    state_dict['scheduler'] = scheduler.state_dict()   # (the reference's loader ignores the key)
                 logging.info(f'save state to {state_path}')
                 _atomic_save(state_dict, state_path)
                 for name in errs:
@@ -515,8 +526,6 @@ class Worker(object):
                         min_err[name] = err
                         _atomic_save(state_dict, self.exp_output_dir / f'state_set_{name}_best.dict')
                 _atomic_save(net.state_dict(), self.get_net_path(epoch))
-            if scheduler is not None:
-                scheduler.step()
             if self.world_size > 1:
                 torch.distributed.barrier()
 

@@ -2611,6 +2611,27 @@ def adam_step_dev(param, grad, exp_avg, exp_avg_sq, state, lr=1e-4, beta1=0.9, b
     params_changed()   # what this step's batch launch packed is stale (inference before the next step packs per call)
 
 
+def adam_step_hyper(param, grad, exp_avg, exp_avg_sq, state, hyper, stats=None, partials=None, mode=0, beta1=0.9,
+                    beta2=0.999, eps=1e-8, grad_scale=1.0):
+    """adam_step_dev with the learning rate (hyper[0]) and max_norm (hyper[1]) read from the 4-float device tensor `hyper`, and,
+    with mode bit 0 / bit 1, clip-by-global-norm / skip-on-a-non-finite-norm decided on the device (`stats`: 4 doubles {norm,
+    coefficient, skipped steps, skipped this call}; `partials`: dis_adam_step_hyper_workspace doubles).  Safe to capture."""
+    _chk(param, grad, exp_avg, exp_avg_sq)
+    if not state.is_cuda or state.dtype != torch.int32 or state.numel() < 4:
+        raise RuntimeError('adam_step_hyper: state must be a 4-element int32 CUDA(HIP) tensor')
+    if not hyper.is_cuda or hyper.dtype != torch.float32 or hyper.numel() < 4:
+        raise RuntimeError('adam_step_hyper: hyper must be a 4-element float32 CUDA(HIP) tensor')
+    if mode != 0:
+        if stats is None or not stats.is_cuda or stats.dtype != torch.float64 or stats.numel() < 4:
+            raise RuntimeError('adam_step_hyper: stats must be a 4-element float64 CUDA(HIP) tensor')
+        need = lib.fn('dis_adam_step_hyper_workspace')(param.numel())
+        if partials is None or not partials.is_cuda or partials.dtype != torch.float64 or need < 0 or partials.numel() < need:
+            raise RuntimeError(f'adam_step_hyper: partials must be a float64 CUDA(HIP) tensor of {need} elements')
+    lib.call('dis_adam_step_hyper', param, grad, exp_avg, exp_avg_sq, param.numel(), hyper, float(beta1), float(beta2),
+             float(eps), state, stats, partials, int(mode), float(grad_scale))
+    params_changed()   # (as adam_step_dev)
+
+
 def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
     _chk(param, grad, exp_avg, exp_avg_sq)
     params_changed()

@@ -1,6 +1,7 @@
 """Optimiser and data-parallel plumbing of the step: one flat fp32 parameter / gradient buffer, a fused Adam kernel over
-it (dis_adam_step_dev: step counter on the device, so a captured step replays correctly) and the gradient all-reduce
-over RCCL (torch.distributed 'nccl'), bucketed and overlapped with the backward pass.
+it (dis_adam_step_hyper: step counter, learning rate and the clip / skip decision on the device, so a captured step replays
+correctly and honours a learning rate changed between replays), a LambdaLR-style schedule, and the gradient all-reduce over
+RCCL (torch.distributed 'nccl'), bucketed and overlapped with the backward pass.
 
 The reference uses torch.optim.Adam(lr=1e-4) on a single GPU (train_val.py:55-56) and has no communication layer; data
 parallelism here is batch sharding with mean-of-per-rank gradients: rank r owns its own tracks,
@@ -91,10 +92,18 @@ class FlatAdam(object):
     parameter is learnt in the first step (which reduces everything after backward, like overlap=False); a later step
     that notifies differently fails loudly.  step() waits for the collectives and runs the fused Adam kernel with
     grad_scale = 1/world_size (mean of the per-rank gradients).  Inside a hipGraph capture the hooks stay silent: the
-    caller places all_reduce_grads() between captured segments (bench.py)."""
+    caller places all_reduce_grads() between captured segments (bench.py).
+
+    Hyper-parameters live in `param_groups[0]` (a real dict, torch.optim's layout: `for g in opt.param_groups: g['lr'] *= 0.5`
+    works, and so does `opt.lr = x`) and are mirrored in `hyper_dev`, which the kernel reads: sync_hyper() uploads them when
+    they changed, so a captured step follows a scheduler without re-capture.
+    max_grad_norm: clip by global L2 norm (torch.nn.utils.clip_grad_norm_; with world_size > 1 the norm of the MEAN gradient,
+    taken after the all-reduce, so every rank decides alike).  skip_nonfinite: a step whose gradient norm is inf / NaN changes
+    nothing and is counted.  Both are decided on the device.  Which of the two are on (`mode`) is fixed at construction - it
+    decides which kernels a captured step contains; the VALUE of max_grad_norm may change at any time."""
 
     def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, world_size=None, process_group=None,
-                 bucket_mb=16.0, overlap=True):
+                 bucket_mb=16.0, overlap=True, max_grad_norm=None, skip_nonfinite=False):
         self.params = [p for p in params]
         assert len(self.params) > 0
         dev = self.params[0].device
@@ -107,6 +116,11 @@ class FlatAdam(object):
         self.exp_avg_sq = torch.zeros(pad, dtype=torch.float32, device=dev)
         # {int steps taken, float 1-beta1^t, float sqrt(1-beta2^t), unused}: advanced by dis_adam_step_dev on the device
         self.state_dev = torch.zeros(4, dtype=torch.int32, device=dev)
+        # {lr, max_norm, reserved, reserved}: what the kernel reads; written by sync_hyper() only
+        self.hyper_dev = torch.zeros(4, dtype=torch.float32, device=dev)
+        # {gradient norm, clip coefficient, skipped steps, skipped the last step}: written by the kernel when mode != 0
+        self.stats_dev = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.stats_dev[1] = 1.0
         self.offsets = []
         off = 0
         with torch.no_grad():
@@ -117,7 +131,13 @@ class FlatAdam(object):
                 p.grad = self.flat_g[off:off + k].view(p.shape)
                 self.offsets.append(off)
                 off += k
-        self.lr, self.betas, self.eps = lr, betas, eps
+        self.param_groups = [{'lr': lr, 'betas': tuple(betas), 'eps': eps, 'weight_decay': 0, 'amsgrad': False,
+                              'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False,
+                              'fused': None, 'max_grad_norm': None if max_grad_norm is None else float(max_grad_norm),
+                              'skip_nonfinite': bool(skip_nonfinite), 'params': list(range(len(self.params)))}]
+        self._uploaded = None      # (lr, max_norm) as last written to hyper_dev
+        self.partials = None
+        self._set_mode((1 if max_grad_norm is not None else 0) | (2 if skip_nonfinite else 0))
         if world_size is None:
             world_size = torch.distributed.get_world_size(process_group) if torch.distributed.is_initialized() else 1
         self.world_size = world_size
@@ -249,19 +269,92 @@ class FlatAdam(object):
     def step_count(self):
         return int(self.state_dev[0])  # device -> host: only checkpointing / tests read it
 
+    # ------------------------------------------------------------------ hyper-parameters: host dict <-> hyper_dev
+    def _set_mode(self, mode):
+        self.mode = mode
+        if mode != 0 and self.partials is None:
+            k = ops.lib.fn('dis_adam_step_hyper_workspace')(self.flat_p.numel())
+            if k < 0:
+                raise RuntimeError(f'FlatAdam: no gradient-norm kernel for {self.flat_p.numel()} parameters')
+            self.partials = torch.empty(k, dtype=torch.float64, device=self.flat_p.device)
+
+    lr = property(lambda self: self.param_groups[0]['lr'],
+                  lambda self, v: self.param_groups[0].__setitem__('lr', v))
+    betas = property(lambda self: self.param_groups[0]['betas'],
+                     lambda self, v: self.param_groups[0].__setitem__('betas', tuple(v)))
+    eps = property(lambda self: self.param_groups[0]['eps'],
+                   lambda self, v: self.param_groups[0].__setitem__('eps', v))
+    skip_nonfinite = property(lambda self: bool(self.mode & 2))
+
+    @property
+    def max_grad_norm(self):
+        return self.param_groups[0]['max_grad_norm']
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        if (v is None) != (not self.mode & 1):
+            raise ValueError('FlatAdam: clipping is turned on or off at construction (it decides which kernels a captured '
+                             'step contains); only the value of max_grad_norm can change later')
+        self.param_groups[0]['max_grad_norm'] = None if v is None else float(v)
+
+    def _host_hyper(self):
+        g = self.param_groups[0]
+        mn = g.get('max_grad_norm')
+        if (mn is None) != (not self.mode & 1) or bool(g.get('skip_nonfinite', False)) != bool(self.mode & 2):
+            raise ValueError('FlatAdam: max_grad_norm / skip_nonfinite were turned on or off after construction')
+        return (float(g['lr']), 0.0 if mn is None else float(mn))
+
+    def sync_hyper(self):
+        """hyper_dev = the host's (lr, max_norm) if they changed since the last upload: a stream-ordered copy on the current
+        stream, nothing otherwise.  Issues nothing inside a capture and raises there if the device copy is stale."""
+        want = self._host_hyper()
+        if want == self._uploaded:
+            return
+        if self.hyper_dev.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FlatAdam: hyper-parameters changed inside a capture; call sync_hyper() before capturing')
+        self._hyper_host = torch.tensor([want[0], want[1], 0.0, 0.0], dtype=torch.float32)
+        self.hyper_dev.copy_(self._hyper_host, non_blocking=True)
+        self._uploaded = want
+
+    # for logging and tests only: each read is a device -> host synchronisation
+    @property
+    def last_grad_norm(self):
+        """global L2 norm of the (mean) gradient of the last step (mode != 0)"""
+        return float(self.stats_dev[0])
+
+    @property
+    def last_clip_coef(self):
+        """clip coefficient of the last step (1.0: not clipped)"""
+        return float(self.stats_dev[1])
+
+    @property
+    def skipped_steps(self):
+        """number of steps skipped for a non-finite gradient so far"""
+        return int(self.stats_dev[2])
+
     def step(self, all_reduce=True):
         # every GroupNorm token of this backward pass redeemed, every pre-reduced gradient picked up - checked BEFORE the update
         # (a stale table means gradients of this step are wrong; the next zero_grad() would be one update too late)
         ops.check_backward_complete()
         if all_reduce:
             self.finish_grads()
-        ops.adam_step_dev(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.state_dev, self.lr,
-                          self.betas[0], self.betas[1], self.eps, 1.0 / self.world_size)
+        self.sync_hyper()
+        ops.adam_step_hyper(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.state_dev, self.hyper_dev,
+                            self.stats_dev, self.partials, self.mode, self.betas[0], self.betas[1], self.eps,
+                            1.0 / self.world_size)
 
     def broadcast_parameters(self, src=0):
-        """identical replicas: parameters, moments and the step counter of rank `src`"""
+        """identical replicas: parameters, moments, the step counter, the hyper-parameters and the clip / skip statistics of
+        rank `src`"""
         if self.world_size > 1:
-            for t in (self.flat_p, self.exp_avg, self.exp_avg_sq, self.state_dev):
+            g = self.param_groups[0]
+            hyper = [g['lr'], g['max_grad_norm']]
+            torch.distributed.broadcast_object_list(hyper, src=src, group=self.process_group)
+            g['lr'] = hyper[0]
+            if self.mode & 1:
+                g['max_grad_norm'] = hyper[1]
+            self.sync_hyper()
+            for t in (self.flat_p, self.exp_avg, self.exp_avg_sq, self.state_dev, self.stats_dev):
                 torch.distributed.broadcast(t, src, group=self.process_group)
             ops.params_changed()   # (weights packed by this step's batch launch are stale)
 
@@ -275,9 +368,9 @@ class FlatAdam(object):
                 k = p.numel()
                 state[i] = {'step': torch.tensor(step), 'exp_avg': self.exp_avg[off:off + k].view(p.shape).clone(),
                             'exp_avg_sq': self.exp_avg_sq[off:off + k].view(p.shape).clone()}
-        group = {'lr': self.lr, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': 0, 'amsgrad': False,
-                 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-                 'params': list(range(len(self.params)))}
+        group = dict(self.param_groups[0], betas=tuple(self.betas), params=list(range(len(self.params))))
+        if self.mode == 0:   # (plain Adam: exactly torch.optim.Adam's keys)
+            del group['max_grad_norm'], group['skip_nonfinite']
         return {'state': state, 'param_groups': [group]}
 
     def load_state_dict(self, sd):
@@ -294,6 +387,13 @@ class FlatAdam(object):
         if g0.get('amsgrad') or g0.get('weight_decay', 0) or g0.get('maximize'):
             raise ValueError('only plain Adam (no amsgrad / weight decay / maximize) is supported')
         self.lr, self.betas, self.eps = float(g0['lr']), tuple(g0['betas']), float(g0['eps'])
+        # (sync_hyper() uploads the learning rate before the next step.)  Clipping / skipping as saved; a state without the keys
+        # - torch.optim.Adam's, the reference's - leaves this optimiser's own settings alone
+        if 'max_grad_norm' in g0 or 'skip_nonfinite' in g0:
+            mn = g0.get('max_grad_norm')
+            self.param_groups[0]['max_grad_norm'] = None if mn is None else float(mn)
+            self.param_groups[0]['skip_nonfinite'] = bool(g0.get('skip_nonfinite', False))
+            self._set_mode((1 if mn is not None else 0) | (2 if g0.get('skip_nonfinite', False) else 0))
         steps = set()
         self.exp_avg.zero_()
         self.exp_avg_sq.zero_()
@@ -380,9 +480,11 @@ class GraphedStep(object):
 
     def _capture(self):
         opt = self.opt
+        opt.sync_hyper()   # (the capture itself may not upload; replays follow the host values through run())
         # the warm-up steps (kernel attributes, allocator pools, autograd nodes on the capture-compatible stream) must not train:
-        # parameters, moments and the step counter are put back afterwards, so a graphed run takes exactly the steps an eager one does
-        state = (opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.state_dev)
+        # parameters, moments, the step counter and the skipped-step count are put back afterwards, so a graphed run takes exactly
+        # the steps an eager one does
+        state = (opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.state_dev, opt.stats_dev)
         snap = [t.clone() for t in state]
         side = torch.cuda.Stream(device=self.dev)
         side.wait_stream(torch.cuda.current_stream())
@@ -407,8 +509,9 @@ class GraphedStep(object):
         if not self.use_graph:
             self._eager()
             return
-        if self._graphs is None or self._key != self.key():
-            self._graphs, self._key = None, self.key()
+        key = (self.key(), self.opt.mode)   # (mode: which optimiser kernels the graph holds; load_state_dict may change it)
+        if self._graphs is None or self._key != key:
+            self._graphs, self._key = None, key
             try:
                 self._capture()
             except Exception as e:  # pragma: no cover
@@ -422,7 +525,50 @@ class GraphedStep(object):
                 torch.cuda.synchronize()
                 self._eager()
                 return
+        self.opt.sync_hyper()   # a learning rate / max_norm changed since the last replay: one small upload, no re-capture
         self._graphs[0].replay()
 
     def losses(self):
         return [float(v) for v in self.loss_buf[:self.nterms].cpu()]
+
+
+class LRSchedule(object):
+    """lr = base_lr * lr_lambda(epoch): torch.optim.lr_scheduler.LambdaLR's contract (construction is epoch 0; step() goes to the
+    next epoch) on anything that has `param_groups` - FlatAdam, which torch's own schedulers refuse, or a torch optimiser.  It only
+    edits `param_groups[...]['lr']`; FlatAdam uploads the value before its next step or replay (sync_hyper).  Worker.train calls
+    step() after every epoch, like the reference (model/worker.py:404-405).  As with LambdaLR, the lambda itself is not saved."""
+
+    def __init__(self, optimizer, lr_lambda, last_epoch=-1):
+        self.optimizer = optimizer
+        self.lr_lambda = lr_lambda
+        if last_epoch == -1:
+            self.base_lrs = [g['lr'] for g in optimizer.param_groups]
+        else:   # resuming without a state_dict: the optimiser must carry the initial learning rate, as torch demands
+            self.base_lrs = [g['initial_lr'] for g in optimizer.param_groups]
+        self.last_epoch = last_epoch
+        self.step()
+
+    def step(self):
+        self.last_epoch += 1
+        self._last_lr = [b * self.lr_lambda(self.last_epoch) for b in self.base_lrs]
+        for g, v in zip(self.optimizer.param_groups, self._last_lr):
+            g['lr'] = v
+
+    def get_last_lr(self):
+        return list(self._last_lr)
+
+    def state_dict(self):
+        return {'last_epoch': self.last_epoch, 'base_lrs': list(self.base_lrs), '_last_lr': list(self._last_lr)}
+
+    def load_state_dict(self, sd):
+        self.last_epoch = int(sd['last_epoch'])
+        self.base_lrs = list(sd['base_lrs'])
+        self._last_lr = list(sd.get('_last_lr', [b * self.lr_lambda(self.last_epoch) for b in self.base_lrs]))
+
+
+def step_decay(step_size, gamma):
+    """lr_lambda of torch.optim.lr_scheduler.StepLR: the learning rate times `gamma` every `step_size` epochs"""
+    step_size = int(step_size)
+    if step_size <= 0:
+        raise ValueError('step_decay: step_size must be positive')
+    return lambda epoch: gamma ** (epoch // step_size)

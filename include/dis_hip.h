@@ -754,6 +754,25 @@ int dis_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
  * step k's bias correction (dis_adam_step would replay the capture-time correction). */
 int dis_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, float lr,
                       double beta1, double beta2, float eps, int* state, float grad_scale, void* stream);
+/* dis_adam_step_dev with the hyper-parameters and the clip / skip decision on the device as well, so that a captured step
+ * honours a learning rate changed between replays and clips without the host looking at the gradient.
+ *   hyper:    4 floats on the DEVICE {learning rate, max_norm (read only when mode & 1), reserved, reserved}.
+ *   state:    as in dis_adam_step_dev.
+ *   mode:     bit 0: clip by global L2 norm, coefficient min(1, max_norm / (norm + 1e-6)) in fp64 (torch.nn.utils.clip_grad_norm_;
+ *             a non-finite norm without bit 1 gives a NaN coefficient that propagates, as in torch); bit 1: skip the step - param,
+ *             moments and state untouched - when the squared norm is not finite (gradients of 1e30 are finite: sums are fp64).
+ *             0: no norm pass, two launches, the bits of dis_adam_step_dev at the same learning rate; so is any step whose
+ *             coefficient is exactly 1.
+ *   stats:    4 doubles on the DEVICE, written when mode != 0: {L2 norm of grad * grad_scale, coefficient applied, running count of
+ *             skipped steps (only ever incremented: zero it once), 1.0 if this call skipped else 0.0}.
+ *   partials: dis_adam_step_hyper_workspace(count) doubles (< 0: unsupported count); needs no initialisation.  stats and partials
+ *             may be NULL when mode == 0.
+ * The norm repeats bit for bit, on any device: one workgroup per fixed-size range of `grad`, every summation order fixed, no atomics.
+ * No host synchronisation, no allocation: safe to capture.  `mode` decides which kernels are launched - a property of the capture. */
+long dis_adam_step_hyper_workspace(long count);
+int dis_adam_step_hyper(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long count, const float* hyper,
+                        double beta1, double beta2, float eps, int* state, double* stats, double* partials, int mode,
+                        float grad_scale, void* stream);
 
 /* ---------------------------------------------------------------- gradient exchange -------- */
 

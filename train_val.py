@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 from depthinspace_amd.co.args import parse_args
 from depthinspace_amd.model import multi_frame_worker, multi_frame_networks, single_frame_worker, networks
-from depthinspace_amd.trainer import FlatAdam, init_distributed
+from depthinspace_amd.trainer import FlatAdam, LRSchedule, init_distributed, step_decay
 from depthinspace_amd import synth
 
 
@@ -47,8 +47,11 @@ def main():
         net = multi_frame_networks.FuseNet(imsize=worker.imsizes[0], K=worker.K, baseline=worker.baseline,
                                            track_length=worker.track_length,
                                            max_disp=args.max_disp).to(worker.train_device)
-    optimizer = FlatAdam(net.parameters(), lr=1e-4)   # world size / process group from torch.distributed
-    worker.do(net, optimizer, cmd=args.cmd, epoch=args.epoch)
+    # world size / process group from torch.distributed; without flags: the reference's Adam(lr=1e-4), no scheduler
+    optimizer = FlatAdam(net.parameters(), lr=args.lr, max_grad_norm=args.max_grad_norm,
+                         skip_nonfinite=args.skip_nonfinite)
+    scheduler = LRSchedule(optimizer, step_decay(args.lr_step, args.lr_gamma)) if args.lr_step > 0 else None
+    worker.do(net, optimizer, cmd=args.cmd, epoch=args.epoch, scheduler=scheduler)
     if world > 1:
         torch.distributed.destroy_process_group()
 
