@@ -160,6 +160,7 @@ SIGS = {
     'dis_adam_step_dev': 'pppplfddfpfp',
     'dis_adam_step_hyper_workspace': 'l',
     'dis_adam_step_hyper': 'pppplpddfpppifp',
+    'dis_assemble_tracks': 'plpppiiiip',
     'dis_allreduce_unique_id': 'p',
     'dis_allreduce_init': 'ppii',
     'dis_allreduce_sum_f32': 'pplip',
@@ -172,6 +173,18 @@ _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_wor
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}
 _lib = None
+
+# include/dis_hip.h: DisTrackLayout (float offsets inside a packed record, -1: absent) and DisTrackOut (device pointers, NULL: not
+# wanted) of dis_assemble_tracks - host-side tables, passed by address
+TRACK_FIELDS = ('im', 'ambient', 'disp', 'sgm_disp', 'primary_disp', 'pseudo_gt', 'flow', 'R', 't')
+
+
+class TrackLayout(ctypes.Structure):
+    _fields_ = [(n_, ctypes.c_long) for n_ in TRACK_FIELDS]
+
+
+class TrackOut(ctypes.Structure):
+    _fields_ = [(n_, ctypes.c_void_p) for n_ in TRACK_FIELDS]
 
 
 def load():

@@ -253,13 +253,21 @@ class Worker(object):
     # ------------------------------------------------------------------ the hot path
     def copy_data(self, data, device, requires_grad, train):
         """reference :418-452.  (bs,tl,...) loader tensors -> self.data with (tl,bs,...) device tensors;
-        `im0` becomes cat(LCN(im0), im0) and `std0` is stored."""
+        `im0` becomes cat(LCN(im0), im0) and `std0` is stored.  A batch of the packed loader (data/packed.py) is assembled on
+        the device (one launch) and taken as it is: already there, already (tl,bs,...)."""
+        from ..data.packed import AssembledBatch, PackedBatch
+        if isinstance(data, PackedBatch):
+            data = data.assemble()
         self.data = {}
-        for key, val in data.items():
-            val = torch.as_tensor(val)
-            if len(val.shape) > 2:
-                val = val.transpose(0, 1)
-            self.data[key] = val.to(device).contiguous()
+        if isinstance(data, AssembledBatch):
+            for key, val in data.items():
+                self.data[key] = val.to(device)
+        else:
+            for key, val in data.items():
+                val = torch.as_tensor(val)
+                if len(val.shape) > 2:
+                    val = val.transpose(0, 1)
+                self.data[key] = val.to(device).contiguous()
         if '_flow_stacked' in self.data:
             # all ordered-pair flows delivered as one (bs, tl*tl, 2, H, W) tensor (entry i*tl+j): after the
             # transpose it is exactly the stacked layout the network consumes; flow_ij become views of it
@@ -327,6 +335,14 @@ class Worker(object):
     def _loader(self, dset, batch_size, train, epoch):
         from ..data.dataset import collate
         sampler = ShardSampler(len(dset), self.rank, self.world_size, shuffle=train, seed=self.seed, epoch=epoch)
+        if self.data_root is not None and (self.data_root / 'packed.json').exists() and hasattr(dset, 'sample_paths'):
+            # a packed root (data/packed.py; nothing else selects this path): reader threads, one upload per batch, assembly on
+            # the device.  Seeded like _seed_loader_worker's worker 0.
+            from ..data import packed
+            dev = self.train_device if train else self.test_device
+            return packed.loader_for(dset, list(sampler), batch_size, train, min(self.num_workers, 8),
+                                     (self.seed + 1000 * self.rank + 7919 * self.current_epoch) % (2 ** 31),
+                                     dev if 'cuda' in str(dev) and torch.cuda.is_available() else None, str(self.data_root))
         return torch.utils.data.DataLoader(dset, batch_size=batch_size, sampler=sampler, num_workers=self.num_workers,
                                            drop_last=train, pin_memory=train, collate_fn=collate,
                                            worker_init_fn=self._seed_loader_worker)
@@ -353,14 +369,15 @@ class Worker(object):
                 break
             if self.use_graph:
                 graphed = self._graphed_step(net, optimizer, data)
-                data = dict(data)
+                packed = data if hasattr(data, 'assemble') else None   # (a PackedBatch: assembled into the static buffers by run())
+                data = dict(data) if packed is None else {}
                 if self.device_aug:
-                    im = data['im0']
-                    data['_aug_params'], data['_aug_seed'] = self.draw_aug(im.shape[0] * im.shape[1])
+                    n_img = packed.bs * packed.tl if packed is not None else data['im0'].shape[0] * data['im0'].shape[1]
+                    data['_aug_params'], data['_aug_seed'] = self.draw_aug(n_img)
                 if self.data_type == 'real' and self.current_epoch < self.warmup_epochs:
                     for k in range(self.n_sgm_draws):  # host generator, as the reference
-                        data[f'_sgm_noise{k}'] = 1.5 * torch.randn(data['sgm_disp'].shape)
-                graphed.run(data)
+                        data[f'_sgm_noise{k}'] = 1.5 * torch.randn(graphed.static['sgm_disp'].shape)
+                graphed.run(data, packed=packed)
                 stacked = graphed.loss_buf[:graphed.nterms].clone()
                 errs, output = list(stacked), None
             else:
@@ -398,7 +415,10 @@ class Worker(object):
         """the captured step of this (net, optimizer, batch shapes): built once and kept across epochs (static buffers,
         warm-up steps and the capture are paid once; GraphedStep.key() re-captures when the set of loss terms changes)"""
         from ..trainer import GraphedStep
-        sig = (id(net), id(optimizer), tuple((k, tuple(torch.as_tensor(v).shape)) for k, v in sorted(example_batch.items())))
+        if hasattr(example_batch, 'assemble'):
+            sig = (id(net), id(optimizer), example_batch.signature())
+        else:
+            sig = (id(net), id(optimizer), tuple((k, tuple(torch.as_tensor(v).shape)) for k, v in sorted(example_batch.items())))
         cached = getattr(self, '_graphed', None)
         if cached is not None and cached[0] == sig:
             return cached[1]
@@ -408,7 +428,10 @@ class Worker(object):
 
     def _build_graphed_step(self, net, optimizer, example_batch):
         from ..trainer import GraphedStep
-        ex = dict(example_batch)
+        if hasattr(example_batch, 'assemble'):   # a PackedBatch: the static buffers are the assembled keys, (tl,bs,...) on the device
+            ex = example_batch.assemble(release=False)
+        else:
+            ex = dict(example_batch)
         if self.device_aug:
             im = ex['im0']
             ex['_aug_params'], ex['_aug_seed'] = self.draw_aug(im.shape[0] * im.shape[1])

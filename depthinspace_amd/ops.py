@@ -2637,3 +2637,54 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, beta1=0.9, beta2=
     params_changed()
     lib.call('dis_adam_step', param, grad, exp_avg, exp_avg_sq, param.numel(), float(lr), float(beta1), float(beta2),
              float(eps), int(step), float(grad_scale))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# batch assembly for packed track files (data/packed.py)
+# ----------------------------------------------------------------------------------------------------------------------
+# DisTrackOut field -> (batch key, trailing shape after (tl, bs)); flow: (tl * tl, bs, 2, h, w)
+_TRACK_KEYS = {'im': 'im0', 'ambient': 'ambient0', 'disp': 'disp0', 'sgm_disp': 'sgm_disp', 'primary_disp': 'primary_disp',
+               'pseudo_gt': 'pseudo_gt', 'flow': '_flow_stacked', 'R': 'R', 't': 't'}
+
+
+def assemble_tracks(raw, perm, bs, tl, h, w, has_sgm=False, primary=False, pseudo=False, want_sgm=None, flows=True,
+                    record_stride=None, out=None):
+    """dis_assemble_tracks: `bs` packed records (data.packed.record_layout(h, w, has_sgm, primary, pseudo); record b at
+    raw[b * record_stride:], default stride: the record size) and the (bs, tl) int32 frame orders `perm` -> the step's inputs in
+    their final layout, one launch on the current stream: im0 / ambient0 / disp0 [/ sgm_disp / primary_disp / pseudo_gt]
+    (tl, bs, 1, h, w), R (tl, bs, 3, 3), t (tl, bs, 3), _flow_stacked (tl * tl, bs, 2, h, w) with zero i == j planes.
+    want_sgm: deliver sgm_disp (default: when the records have it); flows=False: no _flow_stacked.  out: a dict holding
+    tensors of exactly these shapes to write into (the static buffers of a captured step); default: fresh tensors.  Returns a
+    data.packed.AssembledBatch (a dict that Worker.copy_data takes as it is)."""
+    from .data import packed as _packed
+    lay = _packed.record_layout(h, w, has_sgm, primary, pseudo)
+    stride = lay['size'] if record_stride is None else int(record_stride)
+    if not (isinstance(raw, torch.Tensor) and raw.is_cuda and raw.dtype == torch.float32 and raw.dim() == 1 and raw.is_contiguous()):
+        raise RuntimeError('assemble_tracks: raw must be a contiguous 1-D float32 CUDA(HIP) tensor: the HIP path is the only path')
+    if not (perm.is_cuda and perm.dtype == torch.int32 and perm.is_contiguous() and tuple(perm.shape) == (bs, tl)):
+        raise RuntimeError(f'assemble_tracks: perm must be a contiguous int32 CUDA(HIP) tensor of shape ({bs}, {tl})')
+    if bs > 0 and stride > 0 and raw.numel() < (bs - 1) * stride + lay['size']:
+        raise RuntimeError(f'assemble_tracks: raw holds {raw.numel()} floats, {bs} records of stride {stride} need '
+                           f'{(bs - 1) * stride + lay["size"]}')
+    want = {'im': True, 'ambient': True, 'disp': True, 'R': True, 't': True, 'flow': bool(flows), 'primary_disp': bool(primary),
+            'pseudo_gt': bool(pseudo), 'sgm_disp': bool(has_sgm) if want_sgm is None else bool(want_sgm)}
+    shapes = {'R': (tl, bs, 3, 3), 't': (tl, bs, 3), 'flow': (tl * tl, bs, 2, h, w)}
+    L, O = lib.TrackLayout(), lib.TrackOut()
+    res = _packed.AssembledBatch()
+    for f in lib.TRACK_FIELDS:
+        setattr(L, f, lay.get(f, -1))
+        if not want[f]:
+            continue
+        shape = shapes.get(f, (tl, bs, 1, h, w))
+        if out is None:
+            t = torch.empty(shape, dtype=torch.float32, device=raw.device)
+        else:
+            t = out[_TRACK_KEYS[f]]
+            _chk(t)
+            if tuple(t.shape) != shape or t.device != raw.device:
+                raise RuntimeError(f'assemble_tracks: out[{_TRACK_KEYS[f]!r}] is {tuple(t.shape)} on {t.device}, expected {shape} '
+                                   f'on {raw.device}')
+        setattr(O, f, t.data_ptr())
+        res[_TRACK_KEYS[f]] = t
+    lib.call('dis_assemble_tracks', raw, stride, perm, _ct.addressof(L), _ct.addressof(O), int(bs), int(tl), int(h), int(w))
+    return res

@@ -442,7 +442,10 @@ class GraphedStep(object):
         self.strict = strict          # True: a failing capture raises instead of falling back to eager launches
         self.capture_error = None     # why the step runs eagerly although a graph was asked for
         self.dev = opt.flat_p.device
-        self.static = {k: torch.as_tensor(v).to(self.dev).contiguous().clone() for k, v in example_batch.items()}
+        # (type(example_batch): an AssembledBatch of the packed loader stays one, so that copy_data takes the buffers as they are)
+        from .data.packed import AssembledBatch
+        self.static = (AssembledBatch if isinstance(example_batch, AssembledBatch) else dict)(
+            (k, torch.as_tensor(v).to(self.dev).contiguous().clone()) for k, v in example_batch.items())
         self.loss_buf = torch.zeros(32, device=self.dev)
         self.nterms = 0
         self.world = opt.world_size
@@ -502,10 +505,15 @@ class GraphedStep(object):
         self._graphs, self.mode = (g1,), 'graph'
 
     # ---- public
-    def run(self, batch=None):
+    def run(self, batch=None, packed=None):
+        """batch: host (or device) tensors copied into the static buffers.  packed: a data.packed.PackedBatch - the current stream
+        waits for its upload, ONE launch assembles it into the static buffers (outside the capture, in front of the replay) and its
+        device slot is handed back to the loader behind that launch."""
         if batch is not None:
             for k, v in batch.items():
                 self.static[k].copy_(torch.as_tensor(v), non_blocking=True)
+        if packed is not None:
+            packed.assemble(out=self.static)
         if not self.use_graph:
             self._eager()
             return

@@ -742,6 +742,30 @@ int dis_colsum_bf16(const void* G, int ldG, int goff, long npix, int c, float* o
 int dis_augment(const float* im, const float* amb, const float* params, const long long* seed, unsigned* minmax_ws,
                 float* out_im, float* out_amb, int n, int h, int w, void* stream);
 
+/* ---------------------------------------------------------------- batch assembly ------------ */
+
+/* Packed track files (depthinspace_amd/data/packed.py) -> the step's inputs, one launch.  raw: bs records on the DEVICE, record b at
+ * raw + b * record_stride floats; a record holds, at the float offsets of `layout` (HOST struct; -1: the record has no such field),
+ * im / ambient / disp / sgm_disp / primary_disp / pseudo_gt as (4, h, w), flow as (12, 2, h, w) in the pair order 01 02 03 10 12 13
+ * 20 21 23 30 31 32, R (4, 3, 3), t (4, 3).  perm: (bs, tl) ints on the DEVICE, the frame order of every sample; every entry is masked
+ * to 0..3 by the kernel.  `out` (HOST struct of DEVICE pointers; NULL: not wanted; im, ambient, disp, R, t are mandatory):
+ *   out.X[i][b]            = record_b.X[perm[b][i]]                         X (tl, bs, 1, h, w); R (tl, bs, 3, 3); t (tl, bs, 3)
+ *   out.flow[i * tl + j][b] = record_b.flow[pair(perm[b][i], perm[b][j])]   (tl * tl, bs, 2, h, w), pair(p, q) = 3p + q - (q > p);
+ *                             the i == j planes (and those of a table with perm[b][i] == perm[b][j]) are zeros.
+ * Every output element is written, nothing else is: safe in front of a hipGraph replay.  A streaming copy, 16 bytes per lane when
+ * h * w, record_stride and the offsets are multiples of 4 floats and raw and the outputs are 16-byte aligned, 4 bytes otherwise.
+ * Checks, in this order: a NULL raw / perm / layout / out / mandatory output -> DIS_ERR_NULL; bs, tl, h, w <= 0, tl > 4 or a field of
+ * `layout` that does not lie inside [0, record_stride) -> DIS_ERR_BAD_SHAPE; an output whose field `layout` lacks ->
+ * DIS_ERR_UNSUPPORTED.  The caller guarantees bs records behind raw and the output extents above. */
+typedef struct DisTrackLayout {
+  long im, ambient, disp, sgm_disp, primary_disp, pseudo_gt, flow, R, t;
+} DisTrackLayout;
+typedef struct DisTrackOut {
+  float *im, *ambient, *disp, *sgm_disp, *primary_disp, *pseudo_gt, *flow, *R, *t;
+} DisTrackOut;
+int dis_assemble_tracks(const float* raw, long record_stride, const int* perm, const DisTrackLayout* layout, const DisTrackOut* out,
+                        int bs, int tl, int h, int w, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).

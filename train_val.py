@@ -4,7 +4,9 @@
 
 With a config.json (DATA_DIR, OUTPUT_DIR) it trains on the tracks under DATA_DIR (the reference's on-disk schema, .npz
 mirror: depthinspace_amd/data/dataset.py), which is how the three stages chain: DIS-SF -> presave_disp -> DIS-MF ->
-presave_disp -> DIS-FTSF.  Without one it trains on the in-memory synthetic default-pattern scenes of
+presave_disp -> DIS-FTSF.  `python -m depthinspace_amd.data.packed DATA_DIR` after a presave (re)writes the raw copies
+of the tracks that the threaded loader reads (depthinspace_amd/data/packed.py; DATA_DIR/packed.json selects it, nothing
+else does): DIS-SF -> presave_disp -> pack -> DIS-MF.  Without one it trains on the in-memory synthetic default-pattern scenes of
 `depthinspace_amd.synth` (demo / smoke runs).
 
 Data parallel (new; the reference is single-GPU): one process per GPU,
