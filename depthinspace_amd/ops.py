@@ -2688,3 +2688,47 @@ def assemble_tracks(raw, perm, bs, tl, h, w, has_sgm=False, primary=False, pseud
         res[_TRACK_KEYS[f]] = t
     lib.call('dis_assemble_tracks', raw, stride, perm, _ct.addressof(L), _ct.addressof(O), int(bs), int(tl), int(h), int(w))
     return res
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# track rendering (csrc/render.hip; data/render.py samples the scenes and writes the tracks)
+# ----------------------------------------------------------------------------------------------------------------------
+def render_track(verts, faces, albedo, R, t, K, baseline, blend, pattern, want_ids=True, workspace=None):
+    """dis_render_track: the triangle mesh verts (nv, 3) float32 / faces (nf, 3) int32 / albedo (nf) float32 seen by the tl <= 4 cameras
+    R (tl, 3, 3), t (tl, 3) (X_c = R X_w + t) with intrinsics K (3 x 3, host: numpy or a CPU tensor), a rectified projector at
+    +baseline and the (h, w) pattern -> a dict of device tensors: im, ambient, disp (tl, 1, h, w), flow (tl * tl, 2, h, w) (entry
+    i * tl + j = flow_ij, zero diagonal) and, with want_ids, tri_id (tl, h, w) int32 (-1: no triangle) and lit (tl, h, w).  Image
+    formation: include/dis_hip.h, section "track rendering".  Two launches on the current stream; workspace: an optional uint8 tensor
+    of at least dis_render_workspace(...) bytes to reuse between calls."""
+    _chk(verts, albedo, R, t, pattern)
+    if not (faces.is_cuda and faces.dtype == torch.int32 and faces.is_contiguous()):
+        raise RuntimeError('render_track: faces must be a contiguous int32 CUDA(HIP) tensor: the HIP path is the only path')
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or albedo.numel() != faces.shape[0]:
+        raise RuntimeError('render_track: verts (nv, 3), faces (nf, 3) and albedo (nf) are expected')
+    tl = int(R.shape[0])
+    if tuple(R.shape) != (tl, 3, 3) or tuple(t.shape) != (tl, 3) or pattern.dim() != 2:
+        raise RuntimeError('render_track: R (tl, 3, 3), t (tl, 3) and a pattern (h, w) are expected')
+    h, w = int(pattern.shape[0]), int(pattern.shape[1])
+    nv, nf = int(verts.shape[0]), int(faces.shape[0])
+    need = lib.fn('dis_render_workspace')(nv, nf, tl, h, w)
+    if need < 0:
+        raise lib.DisHipError(f'dis_render_workspace: unsupported extents nv={nv} nf={nf} tl={tl} h={h} w={w}')
+    dev = verts.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= need):
+        raise RuntimeError(f'render_track: workspace must be a contiguous uint8 CUDA(HIP) tensor of at least {need} bytes')
+    res = {'im': torch.empty((tl, 1, h, w), dtype=torch.float32, device=dev),
+           'ambient': torch.empty((tl, 1, h, w), dtype=torch.float32, device=dev),
+           'disp': torch.empty((tl, 1, h, w), dtype=torch.float32, device=dev),
+           'flow': torch.empty((tl * tl, 2, h, w), dtype=torch.float32, device=dev)}
+    if want_ids:
+        res['tri_id'] = torch.empty((tl, h, w), dtype=torch.int32, device=dev)
+        res['lit'] = torch.empty((tl, h, w), dtype=torch.float32, device=dev)
+    O = lib.RenderOut()
+    for f, _ in lib.RenderOut._fields_:
+        setattr(O, f, res[f].data_ptr() if f in res else None)
+    K4 = lib.host_floats([K[0][0], K[1][1], K[0][2], K[1][2]])
+    lib.call('dis_render_track', verts, faces, albedo, nv, nf, R, t, K4, float(baseline), float(blend), pattern, _ct.addressof(O),
+             tl, h, w, workspace)
+    return res

@@ -766,6 +766,50 @@ typedef struct DisTrackOut {
 int dis_assemble_tracks(const float* raw, long record_stride, const int* perm, const DisTrackLayout* layout, const DisTrackOut* out,
                         int bs, int tl, int h, int w, void* stream);
 
+/* ---------------------------------------------------------------- track rendering ----------- */
+
+/* A triangle-mesh scene seen by tl cameras -> what a track directory holds (depthinspace_amd/data/render.py writes it out): im,
+ * ambient, disp and the exact rigid flow of every visible surface point for all ordered frame pairs, with occlusion and projector
+ * shadows (csrc/render.hip).  The reference renders its tracks with connecting_the_dots' cyrender on ShapeNet meshes
+ * (data/create_syn_data.py:147-257) and takes its flows from LiteFlowNet; neither is part of this library.
+ * Image formation (the conventions of depthinspace_amd/synth.py, which the loss kernels assume):
+ *   camera     X_c = R X_w + t; pixel (u, v) has the ray ((u - cx) / fx, (v - cy) / fy, 1); depth is the camera-frame z;
+ *              disp = baseline fx / z.
+ *   projector  rectified, centre (+baseline, 0, 0) in the camera frame; a point seen at (u, v) reads pattern(u - disp, v), bilinear
+ *              with border clamp (dis_pattern_warp_fwd's lookup).
+ *   primary    nearest intersection with t > 0 over ALL triangles (a triangle in front of any near distance is never clipped); on
+ *              equal depth the lower triangle index wins.
+ *   shadow     from the hit point to the projector centre: lit = 0 if any triangle other than the hit one meets that segment at a
+ *              parameter in (eps, 1 - eps), eps = 1e-4 (0: the projector, 1: the hit point).  The origin is not offset: the hit
+ *              triangle is excluded by index, a coplanar neighbour by eps.
+ *   shading    face normal n flipped towards the viewer, c / p unit vectors from the point to the camera / projector centre,
+ *              g the triangle's grey albedo, ka = 0.5, kd = 1.5:
+ *                ambient = clip(g (ka + kd max(0, n.c)) / 2, 0, 1)
+ *                P       = clip(g (ka + kd max(0, n.p)) / 2, 0, 1) pattern(u - disp, v) lit
+ *                im      = clip(blend P + (1 - blend) ambient, 0, 1)          (no noise: dis_augment adds it at training time)
+ *   flow       flow[i * tl + j](u, v) = pi_j(X_w) - (u, v) for the surface point visible in frame i, whether or not frame j sees
+ *              it; the i == j planes are zeros.
+ *   miss       disp = 0, flow 0, im = ambient = 0, lit = 0, tri_id = -1.
+ * verts (nv, 3) world coordinates, faces (nf, 3) ints (an index outside [0, nv) is clamped, never followed), albedo (nf), R (tl, 3, 3),
+ * t (tl, 3), pattern (h, w): DEVICE.  K4_host: {fx, fy, cx, cy}, HOST values read during the call.  `out`: HOST struct of DEVICE
+ * pointers - im, ambient, disp (tl, 1, h, w) and flow (tl * tl, 2, h, w) are mandatory; tri_id (tl, h, w) ints and lit (tl, h, w) may
+ * be NULL.  Every element of every output given is written.  workspace: dis_render_workspace(nv, nf, tl, h, w) BYTES (-1: an extent
+ * is not supported), 16-byte aligned, no initialisation: per (frame, triangle) the camera-frame triangle, its plane and its screen
+ * boxes; the candidate lists of the tiles live in LDS and never reach memory, so no scene can overflow them.
+ * Two launches, no allocation, no synchronisation, no float atomics: capturable, and two calls on the same input give the same bits.
+ * Checks, in this order: a NULL argument or mandatory output -> DIS_ERR_NULL; nv, nf, tl, h, w <= 0, tl > 4, nf > 2^20, nv > 2^24,
+ * h or w > 8192 -> DIS_ERR_BAD_SHAPE; fx, fy or baseline not positive and finite, blend outside [0, 1], a misaligned workspace ->
+ * DIS_ERR_UNSUPPORTED. */
+typedef struct DisRenderOut {
+  float *im, *ambient, *disp, *flow;
+  int* tri_id;
+  float* lit;
+} DisRenderOut;
+long dis_render_workspace(int nv, int nf, int tl, int h, int w);
+int dis_render_track(const float* verts, const int* faces, const float* albedo, int nv, int nf, const float* R, const float* t,
+                     const float* K4_host, float baseline, float blend, const float* pattern, const DisRenderOut* out, int tl, int h,
+                     int w, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).
