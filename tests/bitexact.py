@@ -210,11 +210,14 @@ def topk9(keys):
 
 
 def conv3d_select(wxyz, wmask, stride):
-    """neighbour ids (tl,bs,ho,wo,9) for all targets: wxyz (tl,slot,bs,3,h,w), wmask (tl,slot,bs,1,h,w)"""
+    """neighbour ids (tl,bs,ho,wo,9) for all targets, in torch.topk's order, from the 9 x slots keys: wxyz (tl,slot,bs,3,h,w),
+    wmask (tl,slot,bs,1,h,w); the slot count is the input's"""
+    slots = wxyz.shape[1]
     out = []
     for ti in range(wxyz.shape[0]):
-        dist, valid = conv3d_keys(wxyz[ti], wmask[ti], stride)
+        dist, valid = conv3d_keys(wxyz[ti], wmask[ti], stride, tl=slots)
         key = np.where(valid > 0, dist, np.finfo(f32).max).astype(f32)
+        assert key.shape[-1] == 9 * slots
         out.append(topk9(key.reshape(-1, key.shape[-1])).reshape(*key.shape[:-1], 9))
     return np.stack(out, 0)
 

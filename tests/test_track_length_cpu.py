@@ -71,13 +71,8 @@ def test_step_golden_track_length(golden_dir, name):
 
 def conv3d_select_tl(wxyz, wmask, stride, tl):
     """tests/bitexact.py's conv3d_select for tl slots: neighbour ids (tl,bs,ho,wo,9) of all targets from the 9 tl keys"""
-    out = []
-    for ti in range(wxyz.shape[0]):
-        dist, valid = B.conv3d_keys(wxyz[ti], wmask[ti], stride, tl=tl)
-        key = np.where(valid > 0, dist, np.finfo(np.float32).max).astype(np.float32)
-        assert key.shape[-1] == 9 * tl
-        out.append(B.topk9(key.reshape(-1, key.shape[-1])).reshape(*key.shape[:-1], 9))
-    return np.stack(out, 0)
+    assert wxyz.shape[1] == tl   # (B.conv3d_select asserts that it ranks 9 x this many keys)
+    return B.conv3d_select(wxyz, wmask, stride)
 
 
 @pytest.mark.parametrize('name', TL_MF_FIXTURES)

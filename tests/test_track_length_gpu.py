@@ -35,12 +35,8 @@ def _stack_flows(flow, tl, bs, h, w):
 def _select_tl(wxyz, wmask, stride, tl):
     """tests/bitexact.py's Conv3D selection over 9 tl candidates: ids (tl,bs,ho,wo,9) in torch.topk's order"""
     from tests import bitexact as B
-    out = []
-    for ti in range(wxyz.shape[0]):
-        dist, valid = B.conv3d_keys(wxyz[ti], wmask[ti], stride, tl=tl)
-        key = np.where(valid > 0, dist, np.finfo(np.float32).max).astype(np.float32)
-        out.append(B.topk9(key.reshape(-1, key.shape[-1])).reshape(*key.shape[:-1], 9))
-    return np.stack(out, 0)
+    assert wxyz.shape[1] == tl
+    return B.conv3d_select(wxyz, wmask, stride)
 
 
 @pytest.mark.parametrize('tl', TLS)
