@@ -1,0 +1,115 @@
+"""Semi-global matching presave: the `sgm_disp` array that `--data_type real` training reads (the warm-up term ops.sgm_l1).
+
+For every track directory of a dataset root, the 4 IR frames of frames.npz are matched against the projector pattern of settings.npz
+(settings.pattern[..., 0]) with ops.sgm_disparity - 9 x 7 census, 8 paths, uniqueness and left-right checks (include/dis_hip.h, section
+"semi-global matching") - and frames.npz is rewritten with sgm_disp (4, 1, H, W) added; invalid pixels hold 0.  The reference takes this
+array from the authors' real dataset and has no code that produces it.  Semi-global matching is also the classical baseline of
+structured-light depth: --report compares it with the stored ground truth through co/metric.py.
+
+    python -m depthinspace_amd.data.presave_sgm ROOT [--ndisp N] [--p1 P1] [--p2 P2] [--uniq U] [--lr L] [--report] [--pack]
+
+Known limit: the workers mask the warm-up term with sgm_disp > 30 (the reference's constant).  With the default synthetic geometry
+(fx * baseline about 10.7) every rendered disparity is below 30, so the term sees no pixel there; it does with a geometry whose near
+disparities exceed 30, as the authors' real sensor has.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from .dataset import load_settings
+from . import packed
+
+REPORT_THRESHOLDS = (0.1, 0.5, 1, 2, 5)
+
+
+def match_frames(im, pattern, ndisp=64, p1=7, p2=60, uniq=5, lr=1, device='cuda'):
+    """im (4, 1, H, W), pattern (H, W) float32 numpy -> sgm_disp (4, 1, H, W) float32 numpy (ops.sgm_disparity on the device)"""
+    from .. import ops
+    dev = torch.device(device)
+    d = ops.sgm_disparity(torch.from_numpy(np.ascontiguousarray(im, dtype=np.float32)).to(dev),
+                          torch.from_numpy(np.ascontiguousarray(pattern, dtype=np.float32)).to(dev), ndisp, p1, p2, uniq, lr)
+    return d.cpu().numpy()
+
+
+def _rewrite_with(path, name, value):
+    """frames.npz plus one array: the other arrays are copied as they are; temporary file, then os.replace"""
+    with np.load(path) as f:
+        arrays = {k: f[k] for k in f.files}
+    arrays[name] = value
+    tmp = path + '.tmp.npz'   # (np.savez appends .npz to any other ending)
+    try:
+        np.savez(tmp, **arrays)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def sgm_report(data_root):
+    """co/metric.py's DistanceMetric and OutlierFractionMetric of sgm_disp against disp over the pixels where the match is valid
+    (sgm_disp != 0) and the surface was seen (disp > 0), over every track of data_root, plus `valid`: the fraction of the seen pixels
+    with a valid match.  Needs both arrays in every frames.npz."""
+    from ..co import metric
+    m = metric.MultipleMetric(metric.DistanceMetric(vec_length=1), metric.OutlierFractionMetric(vec_length=1, thresholds=REPORT_THRESHOLDS))
+    seen = valid = 0
+    for d in packed.track_dirs(data_root):
+        with np.load(os.path.join(d, 'frames.npz')) as f:
+            if 'sgm_disp' not in f.files or 'disp' not in f.files:
+                raise ValueError(f'{d}/frames.npz: --report needs both sgm_disp and disp')
+            es, ta = torch.from_numpy(f['sgm_disp']).reshape(-1, 1), torch.from_numpy(f['disp']).reshape(-1, 1)
+        ma = (es != 0) & (ta > 0)
+        seen += int((ta > 0).sum())
+        valid += int(ma.sum())
+        m.add(es, ta, ma)
+    res = dict(m.get())
+    res['valid'] = valid / seen if seen else float('nan')
+    return res
+
+
+def presave_sgm(data_root, ndisp=64, p1=7, p2=60, uniq=5, lr=1, report=False, pack=False, device='cuda'):
+    """Adds sgm_disp (4, 1, H, W) to the frames.npz of every track directory of data_root that has none (incremental; the other arrays
+    stay byte-identical; each file is replaced atomically).  pack: re-runs packed.pack_dataset.  Returns the number of tracks matched,
+    or with report=True the dict of sgm_report (printed as one line)."""
+    data_root = str(data_root)
+    pattern = np.ascontiguousarray(load_settings(data_root).pattern[..., 0], dtype=np.float32)
+    done = 0
+    for d in packed.track_dirs(data_root):
+        path = os.path.join(d, 'frames.npz')
+        with np.load(path) as f:
+            if 'sgm_disp' in f.files:
+                continue
+            im = f['im']
+        sgm = np.asarray(match_frames(im, pattern, ndisp, p1, p2, uniq, lr, device), dtype=np.float32).reshape(im.shape)
+        _rewrite_with(path, 'sgm_disp', sgm)
+        done += 1
+    if pack:
+        packed.pack_dataset(data_root)
+    if not report:
+        return done
+    res = sgm_report(data_root)
+    print(f'sgm baseline over {data_root} ({done} tracks matched now): valid {res["valid"]:.4f}  ' +
+          '  '.join(f'{k} {v:.4f}' for k, v in res.items() if k != 'valid'))
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m depthinspace_amd.data.presave_sgm', description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('root')
+    ap.add_argument('--ndisp', type=int, default=64, choices=[64, 128, 256], help='disparity candidates 0 .. ndisp - 1')
+    ap.add_argument('--p1', type=int, default=7)
+    ap.add_argument('--p2', type=int, default=60)
+    ap.add_argument('--uniq', type=int, default=5, help='uniqueness margin in per cent')
+    ap.add_argument('--lr', type=int, default=1, help='left-right tolerance in pixels')
+    ap.add_argument('--report', action='store_true', help='print co/metric.py numbers of sgm_disp against disp')
+    ap.add_argument('--pack', action='store_true', help='also (re)write the packed files (data/packed.py)')
+    a = ap.parse_args(argv)
+    r = presave_sgm(a.root, a.ndisp, a.p1, a.p2, a.uniq, a.lr, report=a.report, pack=a.pack)
+    if not a.report:
+        print(f'{r} tracks matched under {a.root}')
+
+
+if __name__ == '__main__':
+    main()

@@ -6,7 +6,7 @@ that jitter around a base offset and look at (0, 0, 3).  ops.render_track (csrc/
 fixed in include/dis_hip.h, section "track rendering".  The flows are the exact rigid flows of the visible surface points (the
 reference estimates them with LiteFlowNet).
 
-    python -m depthinspace_amd.data.render ROOT --n N [--seed S] [--pattern default|real] [--pack]
+    python -m depthinspace_amd.data.render ROOT --n N [--seed S] [--pattern default|real] [--pack] [--sgm [NDISP]]
 """
 import argparse
 import os
@@ -129,11 +129,13 @@ def render_batch(settings, bs, tl=4, seed=0, objects=None, device=None):
     return out
 
 
-def write_rendered_dataset(root, settings, n, tl=4, seed=0, pack=False, objects=None, device=None):
+def write_rendered_dataset(root, settings, n, tl=4, seed=0, pack=False, objects=None, device=None, sgm=None):
     """Writes tracks 0 .. n - 1 (track i is sample_track(i, tl, seed)) in the on-disk schema of data/dataset.py: settings.npz,
     %08d/frames.npz (im, ambient, grad = zeros, disp (tl, 1, H, W), R, t) and %08d/flow.npz (flow_ij (1, 2, H, W)).  Incremental: a
     track whose two files exist is left alone.  pack: also (re)writes the packed files (data/packed.py).  The training readers expect
-    tl = 4.  Returns the track directories."""
+    tl = 4.  sgm: a candidate count (64, 128 or 256) also stores sgm_disp, the semi-global match of every frame against the pattern
+    (ops.sgm_disparity, the call of data/presave_sgm.py); None: the files are what they were without it.  Returns the track
+    directories."""
     from . import dataset as D
     root = str(root)
     D.save_settings(root, settings)
@@ -152,8 +154,12 @@ def write_rendered_dataset(root, settings, n, tl=4, seed=0, pack=False, objects=
         im, flow = to_np(res['im']), to_np(res['flow'])
         # flow.npz first: frames.npz is what marks a track directory as complete for the readers
         np.savez(os.path.join(d, 'flow.npz'), **{f'flow_{a}{b}': flow[a * tl + b][None] for a in range(tl) for b in range(tl) if a != b})
+        extra = {}
+        if sgm is not None:
+            from .. import ops
+            extra['sgm_disp'] = to_np(ops.sgm_disparity(res['im'], pattern, int(sgm)))
         np.savez(os.path.join(d, 'frames.npz'), im=im, ambient=to_np(res['ambient']), grad=np.zeros_like(im), disp=to_np(res['disp']),
-                 R=R, t=t)
+                 R=R, t=t, **extra)
     if pack:
         from . import packed
         packed.pack_dataset(root)
@@ -167,8 +173,10 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--pattern', choices=['default', 'real'], default='default')
     ap.add_argument('--pack', action='store_true', help='also write the packed files (data/packed.py)')
+    ap.add_argument('--sgm', type=int, nargs='?', const=64, default=None, choices=[64, 128, 256], metavar='NDISP',
+                    help='also store sgm_disp, the semi-global match against the pattern (data/presave_sgm.py), with NDISP candidates')
     a = ap.parse_args(argv)
-    paths = write_rendered_dataset(a.root, synth.make_settings(pattern=a.pattern), a.n, seed=a.seed, pack=a.pack)
+    paths = write_rendered_dataset(a.root, synth.make_settings(pattern=a.pattern), a.n, seed=a.seed, pack=a.pack, sgm=a.sgm)
     print(f'{len(paths)} tracks under {a.root}')
 
 

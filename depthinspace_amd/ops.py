@@ -2732,3 +2732,37 @@ def render_track(verts, faces, albedo, R, t, K, baseline, blend, pattern, want_i
     lib.call('dis_render_track', verts, faces, albedo, nv, nf, R, t, K4, float(baseline), float(blend), pattern, _ct.addressof(O),
              tl, h, w, workspace)
     return res
+
+
+def sgm_disparity(im, pattern, ndisp=64, p1=7, p2=60, uniq=5, lr=1, want_debug=False, workspace=None):
+    """dis_sgm_disparity: 9 x 7 census + 8-path semi-global matching of the IR frames im (n, 1, H, W) or (n, H, W) against the projector
+    pattern (H, W) -> disp with the shape of im, 0 where the match is invalid (include/dis_hip.h, section "semi-global matching";
+    tests/sgm_ref.py restates it in numpy and the kernels equal it bit for bit).  ndisp: 64, 128 or 256 candidates; 0 < p1 < p2 <= 127;
+    uniq in [0, 100) per cent; lr >= 0 pixels.  want_debug: also a dict with d_int (n, H, W) int32 (the winning candidate of every pixel,
+    valid or not), vol (n, H, W, ndisp) int16 (the aggregated cost) and census (n + 1, H, W) int64 (the pattern's last).  The inputs are
+    data: no autograd.  Ten launches on the current stream; workspace: an optional uint8 tensor of at least dis_sgm_workspace(...)
+    bytes to reuse between calls (and what makes the call capturable without an allocation)."""
+    _chk(im, pattern)
+    if not ((im.dim() == 3 or (im.dim() == 4 and im.shape[1] == 1)) and pattern.dim() == 2 and tuple(im.shape[-2:]) == tuple(pattern.shape)):
+        raise RuntimeError('sgm_disparity: im (n, 1, H, W) or (n, H, W) and a pattern (H, W) are expected')
+    n, h, w = int(im.shape[0]), int(im.shape[-2]), int(im.shape[-1])
+    ndisp, p1, p2, uniq, lr = int(ndisp), int(p1), int(p2), int(uniq), int(lr)
+    need = lib.fn('dis_sgm_workspace')(n, h, w, ndisp)
+    if need < 0:
+        raise lib.DisHipError(f'dis_sgm_workspace: unsupported extents n={n} h={h} w={w} ndisp={ndisp}')
+    if not (0 < p1 < p2 <= 127 and 0 <= uniq < 100 and lr >= 0):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'sgm_disparity: unsupported configuration p1={p1} p2={p2} uniq={uniq} lr={lr}')
+    dev = im.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= need):
+        raise RuntimeError(f'sgm_disparity: workspace must be a contiguous uint8 CUDA(HIP) tensor of at least {need} bytes')
+    disp = torch.empty_like(im)
+    dbg = None
+    if want_debug:
+        dbg = {'d_int': torch.empty((n, h, w), dtype=torch.int32, device=dev),
+               'vol': torch.empty((n, h, w, ndisp), dtype=torch.int16, device=dev),
+               'census': torch.empty((n + 1, h, w), dtype=torch.int64, device=dev)}
+    lib.call('dis_sgm_disparity', im, pattern, disp, dbg and dbg['d_int'], dbg and dbg['vol'], dbg and dbg['census'], n, h, w, ndisp,
+             p1, p2, uniq, lr, workspace)
+    return (disp, dbg) if want_debug else disp

@@ -810,6 +810,33 @@ int dis_render_track(const float* verts, const int* faces, const float* albedo, 
                      const float* K4_host, float baseline, float blend, const float* pattern, const DisRenderOut* out, int tl, int h,
                      int w, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- semi-global matching ------ */
+
+/* Classical disparity of IR frames against the projector pattern (csrc/sgm.hip): what `--data_type real` training reads as sgm_disp
+ * (dis_sgm_l1_fwd), and the baseline the networks are compared with.  Geometry as in "track rendering": pixel (u, v) sees
+ * pattern(u - d, v); candidates d = 0 .. ndisp - 1.  Integer arithmetic up to the winning candidate; tests/sgm_ref.py restates it in
+ * numpy and the kernels match it bit for bit.
+ *   census    9 wide x 7 high window, replicate padding; the 62 neighbours in row-major order (dy, dx) = (-3, -4) .. (3, 4) without the
+ *             centre; bit k (value 2^k) = neighbour < centre (strict, fp32, false for NaN).  Every frame, and the pattern once.
+ *   cost      C(u, v, d) = popcount(cI(u, v) xor cP(u - d, v)) for u - d >= 0, else 64.  Never stored.
+ *   paths     8 directions r; where p - r lies outside the image L_r(p, d) = C(p, d); elsewhere, m = min_k L_r(p - r, k),
+ *             L_r(p, d) = C(p, d) + min(L_r(p - r, d), L_r(p - r, d - 1) + p1, L_r(p - r, d + 1) + p1, m + p2) - m
+ *             (no d +- 1 term outside [0, ndisp)).  S = sum_r L_r <= 8 (64 + 127) fits 16 bits.
+ *   winner    d0 = argmin_d S (lowest d on ties), s0 = S(d0), s2 = min S over |d - d0| > 1.  Valid iff 1 <= d0 <= ndisp - 2,
+ *             s2 (100 - uniq) > 100 s0, u - d0 >= 0 and |dR(u - d0, v) - d0| <= lr with dR(x, v) = argmin_d S(x + d, v, d) over
+ *             x + d < w (lowest d on ties).  disp = d0 + (a - c) / (2 (a + c - 2 b)) for a, b, c = S(d0 - 1), S(d0), S(d0 + 1) in fp32
+ *             when a + c - 2 b > 0, else d0; an invalid pixel gets 0.
+ * im (n, h, w), pattern (h, w), disp (n, h, w): DEVICE; every element of disp is written.  Optional outputs (NULL: not wanted): d_int
+ * (n, h, w) = d0 of every pixel, valid or not; vol = S as (n, h, w, ndisp) int16; census (n + 1, h, w) 64-bit words, the pattern's last.
+ * workspace: dis_sgm_workspace(n, h, w, ndisp) BYTES (-1: unsupported extents or ndisp), 16-byte aligned, no initialisation.  Ten
+ * launches, no allocation, no synchronisation, no atomics: capturable, and two calls on the same input give the same bits.
+ * Checks, in this order: NULL im, pattern, disp or workspace -> DIS_ERR_NULL; n, h, w <= 0, h or w > 8192, (n + 1) h w >= 2^31 ->
+ * DIS_ERR_BAD_SHAPE; ndisp not 64, 128 or 256, not 0 < p1 < p2 <= 127, uniq outside [0, 100), lr < 0, a misaligned workspace, vol or census
+ * not 8-byte aligned -> DIS_ERR_UNSUPPORTED. */
+long dis_sgm_workspace(int n, int h, int w, int ndisp);
+int dis_sgm_disparity(const float* im, const float* pattern, float* disp, int* d_int, short* vol, long long* census, int n, int h, int w,
+                      int ndisp, int p1, int p2, int uniq, int lr, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).
