@@ -17,6 +17,18 @@
 extern const char* g_dis_last_kernel;
 #define DIS_TAG(name) (g_dis_last_kernel = (name))
 
+// compute units of the current device (asked once per process; 256 if the query fails)
+static inline int dis_num_cus() {
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
+    if (ncu <= 0) ncu = 256;
+  }
+  return ncu;
+}
+
 static inline int dis_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // grid size for a grid-stride elementwise kernel: enough blocks to fill 256 CUs x 8, never more than needed
 static inline int dis_ew_grid(long work_items, int block) {

@@ -429,17 +429,6 @@ extern "C" int dis_conv2d_pack_weights(const float* w_oihw, float* packed, int c
 // ------------------------------------------------------------------------------------------------
 // launch plumbing
 // ------------------------------------------------------------------------------------------------
-static int g_num_cu = 0;
-static int num_cus() {
-  if (g_num_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      g_num_cu = prop.multiProcessorCount;
-    if (g_num_cu <= 0) g_num_cu = 256;
-  }
-  return g_num_cu;
-}
 
 template <int CIN, int COUT, int KH, int KW, int S, bool GNB = false>
 static int launch_conv(const ConvArgs& a, hipStream_t s) {
@@ -457,7 +446,7 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
   int per_cu = (160 * 1024) / C::LDS_BYTES;
   if (per_cu > 4) per_cu = 4;
   if (per_cu < 1) per_cu = 1;
-  long grid = (long)num_cus() * per_cu;
+  long grid = (long)dis_num_cus() * per_cu;
   if (grid > ntiles) grid = ntiles;
   if (grid >= 8) grid -= grid % 8;
   if (grid < 1) grid = 1;
@@ -1258,7 +1247,7 @@ static int launch_conv_bf16x3(const float* x, const void* w, int wmode, int w_o,
   a.w_rs = w_rs;
   a.xact = xact;
   a.gn_stats = gn.stats; a.gn_gamma = gn.gamma; a.gn_beta = gn.beta; a.gn_eps = gn.eps;
-  a.ab_x = gn.ab_x; a.ab_out = gn.ab_out; a.ab_slots = num_cus(); a.ab_act_y = gn.ab_act_y;
+  a.ab_x = gn.ab_x; a.ab_out = gn.ab_out; a.ab_slots = dis_num_cus(); a.ab_act_y = gn.ab_act_y;
   a.gnb_coef = gn.gnb_coef; a.gnb_out = gn.gnb_out;
   if ((gn.ab_out || gn.gnb_coef) && !(dis_f2_enabled() && wmode >= 0)) return DIS_ERR_UNSUPPORTED;  // (the two-term kernel's forms)
   if (gn.gnb_coef && (!gn.gnb_out || !xact || pad != 1 || cin != cout)) return DIS_ERR_UNSUPPORTED;
@@ -1274,7 +1263,7 @@ static int launch_conv_bf16x3(const float* x, const void* w, int wmode, int w_o,
   if ((long)hin * win * cin * 4 >= 0x7fff0000L || (long)hout * wout * cout * 4 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;
   const int tiles_x = (wout + BX_TC - 1) / BX_TC, tiles_y = (hout + BX_TR - 1) / BX_TR;
   const long ntiles = (long)n * tiles_y * tiles_x;
-  long grid = num_cus();
+  long grid = dis_num_cus();
 #ifdef BX_STAMP
   if (getenv("BX_GRID")) grid = atol(getenv("BX_GRID"));
 #endif
@@ -1362,7 +1351,7 @@ extern "C" int dis_conv2d_fwd_f16x2_gnres(const float* x2, const double* gn_stat
  * one fp64 slot per workgroup: ab_out (n, dis_conv2d_gnsums_slots(), 2, cin) doubles, ZEROED by the caller.  Replaces the
  * reduce pass of dis_gn_apply_bwd (a read of g and x).  Two-term fp16 kernels only (DIS_ERR_UNSUPPORTED otherwise: the caller keeps
  * the two-pass form). */
-extern "C" long dis_conv2d_gnsums_slots(void) { return num_cus(); }
+extern "C" long dis_conv2d_gnsums_slots(void) { return dis_num_cus(); }
 extern "C" int dis_conv2d_dgrad_bf16x3_gnsums(const float* gy, const float* w_oihw, int w_o, int w_i, int w_row_stride, float* g,
                                               const float* gn_x, double* ab_out, int n, int hin, int win, int cin, int cout,
                                               int pad, void* stream) {
@@ -1480,7 +1469,7 @@ int dis_bx_slices_run(int dgrad, const float* x, int ldx, int xoff, int cin, int
   const int ncb_w = (cin_w + 31) / 32;
   const int tiles_x = (wd + BX_TC - 1) / BX_TC, tiles_y = (h + BX_TR - 1) / BX_TR;
   const long ntiles = (long)n * tiles_y * tiles_x;
-  long grid = num_cus();
+  long grid = dis_num_cus();
   if (grid > ntiles) grid = ntiles;
   if (grid >= 8) grid -= grid % 8;
   if (grid < 1) grid = 1;
@@ -1888,7 +1877,7 @@ static int launch_wgrad(WgArgs a, float* gw, float* gb, int cin_real, hipStream_
   }
   const int tiles_x = (a.wout + 15) / 16, tiles_y = (a.hout + C::TROWS - 1) / C::TROWS;
   const long ntiles = (long)a.n * tiles_y * tiles_x;
-  long workers = 2L * num_cus();
+  long workers = 2L * dis_num_cus();
   if (workers > WG_WORKERS) workers = WG_WORKERS;
   if (workers > ntiles) workers = ntiles;
   const long elems = (long)C::NCHUNK * C::NSPLIT * C::PART;
@@ -2231,7 +2220,7 @@ static int launch_wgrad_bf16x3(WgArgs a, float* gw, float* gb, int cin_real, hip
   }
   const int tiles_x = (a.wout + 15) / 16, tiles_y = (a.hout + 7) / 8;
   const long ntiles = (long)a.n * tiles_y * tiles_x;
-  long workers = (dis_f2_enabled() ? (long)dis_f2_wgrad_wpc() : 2L) * num_cus();
+  long workers = (dis_f2_enabled() ? (long)dis_f2_wgrad_wpc() : 2L) * dis_num_cus();
   if (workers > WG_WORKERS) workers = WG_WORKERS;
   if (workers > ntiles) workers = ntiles;
   const long elems = C::PART;
@@ -2321,14 +2310,14 @@ static int bwd_fused_run(const BwdFusedFamily& fam, const float* g, const float*
   a.xact = q;
   a.ldx = a.cx = cg; a.ldy = a.cy = c; a.x_sub = a.y_sub = 0; a.nbias = 0; a.wtap0 = 0; a.wtap_step = 0;
   a.gn_stats = nullptr; a.gn_gamma = nullptr; a.gn_beta = nullptr; a.gn_eps = 0.f;
-  a.ab_x = ab_gn_x; a.ab_out = ab_out; a.ab_slots = !fam.forms ? 0 : (fam.own_slots ? ab_slots : num_cus()); a.ab_act_y = ab_act_y;
+  a.ab_x = ab_gn_x; a.ab_out = ab_out; a.ab_slots = !fam.forms ? 0 : (fam.own_slots ? ab_slots : dis_num_cus()); a.ab_act_y = ab_act_y;
   a.gnb_coef = coef; a.gnb_out = gpre_out; a.gnb_act = 0;
   // x that IS one of the epilogue's operands is fetched once
   const int xsrc = (ab_gn_x && x == ab_gn_x) ? 1 : ((ab_act_y && x == ab_act_y) ? 2 : 0);
   f.wx = x; f.wx_gn_stats = x_gn_stats; f.wx_gn_gamma = x_gn_gamma; f.wx_gn_beta = x_gn_beta; f.wx_gn_eps = x_gn_eps;
   const int tiles_x = (win + 15) / 16, tiles_y = (hin + fam.tile_rows - 1) / fam.tile_rows;
   const long ntiles = (long)n * tiles_y * tiles_x;
-  long grid = (long)fam.wpc * num_cus();
+  long grid = (long)fam.wpc * dis_num_cus();
   if (grid > WG_WORKERS) grid = WG_WORKERS;
   if (fam.own_slots && ab_out && grid > ab_slots) grid = ab_slots;   // (one slot of channel sums per workgroup)
   if (grid > ntiles) grid = ntiles;
@@ -2388,7 +2377,7 @@ extern "C" int dis_conv2d_bwd1x1_scaled_gnb(const float* g, const float* q, cons
   a.g = g; a.q = q; a.coef = coef; a.in_act = in_act; a.w = w_packed_dgrad; a.gx = gx; a.yscale = yscale;
   a.accum = accumulate ? 1 : 0; a.x = x; a.xscale = xscale; a.n = n; a.h = h; a.wd = w;
   const long ntiles = (long)n * ((h + 3) / 4) * ((w + 15) / 16);
-  long grid = 2L * num_cus();   // (two workgroups per CU: 61.5 KB of LDS each)
+  long grid = 2L * dis_num_cus();   // (two workgroups per CU: 61.5 KB of LDS each)
   if (grid > WG_WORKERS) grid = WG_WORKERS;
   if (grid > ntiles) grid = ntiles;
   a.part = workspace;
@@ -2411,7 +2400,7 @@ extern "C" int dis_conv2d_bwd1x1_scaled_gnb(const float* g, const float* q, cons
  * with channel sums runs ab_slots at most - the slots the caller allocated per sample of ab_out and hands to dis_gn_bwd_coef. */
 static int fc_wpc(int cg, int cx) { return cg == cx ? dis_fc_wpc(cg, cx) : dis_fm_wpc(cg, cx); }
 static long fc_max_grid(int cin, int cout) {
-  long g = (long)fc_wpc(cout, cin) * num_cus();
+  long g = (long)fc_wpc(cout, cin) * dis_num_cus();
   return g > WG_WORKERS ? WG_WORKERS : g;
 }
 extern "C" long dis_conv2d_bwd_fused_c16_workspace(int cin, int cout) {
@@ -2513,7 +2502,7 @@ static void wgrad_pairs_plan(int n, int hG, int wG, int cX, int cG, int tr, int*
   *npx = (cX + 31) / 32;
   *ngb = cG == 16 ? 1 : (cG + 31) / 32;
   const long ntiles = (long)n * ((hG + tr - 1) / tr) * ((wG + 15) / 16);
-  long per = (2L * num_cus() + (long)*npx * *ngb - 1) / ((long)*npx * *ngb);  // ~2 workgroups per CU in all
+  long per = (2L * dis_num_cus() + (long)*npx * *ngb - 1) / ((long)*npx * *ngb);  // ~2 workgroups per CU in all
   if (per > ntiles) per = ntiles;
   if (per < 1) per = 1;
   *wpp = (int)per;
@@ -2608,7 +2597,7 @@ static int launch_wgrad_k4s2(WgArgs a, float* gw, float* gb, int cin_real, hipSt
     return gnb.coef ? DIS_ERR_UNSUPPORTED : launch_wgrad<32, 32, 4, 4, 2>(a, gw, gb, cin_real, s);
   const int tiles_x = (a.wout + 15) / 16, tiles_y = (a.hout + 3) / 4;
   const long ntiles = (long)a.n * tiles_y * tiles_x;
-  long workers = 2L * num_cus();
+  long workers = 2L * dis_num_cus();
   if (workers > WG_WORKERS) workers = WG_WORKERS;
   if (workers > ntiles) workers = ntiles;
   const long elems = (long)C::NCHUNK * C::NSPLIT * C::PART;

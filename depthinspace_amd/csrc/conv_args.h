@@ -1,5 +1,5 @@
 // Argument blocks of the convolution kernels and the declarations of their launchers: shared by conv2d.hip (the entry points) and the
-// kernel files (conv_f16x2.hip, conv_gen.hip, conv_k4s2.hip, conv1x1_bwd_fused.hip and the three one-launch 3x3 backward files
+// kernel files (conv_f16x2.hip, conv_gen.hip, conv_bf16.hip, conv_k4s2.hip, conv1x1_bwd_fused.hip and the three one-launch 3x3 backward files
 // conv_bwd_fused*.hip, whose common parts are in conv_bwd_fused_common.h).
 #pragma once
 #include "common.h"
@@ -229,3 +229,20 @@ hipError_t dis_f2_wgrad_pairs_launch(const WgArgs& a, int cob, unsigned workers,
 hipError_t dis_f2_wgrad_k4s2_launch(const WgArgs& a, int gnb_act, long workers, hipStream_t stream);   // 32 -> 32, 4 x 4, stride 2
 bool dis_f2_enabled();
 int dis_f2_wgrad_wpc();   // workgroups per CU the two-term weight-gradient kernel is built for
+
+// conv2d.hip, called from the streaming dispatchers (conv_gen.hip, conv_bf16.hip): 3x3 stride-1 layers as 32 x 32 channel-slice
+// launches of the halo-resident bf16x3 kernel ...
+long dis_bx_slices_ok(int n, int h, int wd, int cin, int cout, int ldx, int ldy, int xoff, int yoff, int k, int stride,
+                      int pad, int act);
+int dis_bx_slices_run(int dgrad, const float* x, int ldx, int xoff, int cin, int cin_w, const float* w,
+                      const float* bias, float* y, int ldy, int yoff, int cout, int cout_w, int n, int h, int wd, int k,
+                      int act, hipStream_t stream);
+// ... and the weight gradient of layers with >= 32 channels on both sides and 3x3 / 5x5 taps as 32 x 32 channel-slice pairs on the
+// one-pass bf16x3 kernel (x halo and gy tile staged once for all taps, accumulators in registers).  bf = 1: bf16 x AND bf16 gy,
+// >= 16 / 32 channels, 3x3 / 5x5 / 7x7 taps (conv_wgrad_bf16x3_kernel<..., BF = true>: one bf16 MFMA product per MAC, operands
+// fetched from the [pixel][channel] LDS images with the transposing read)
+long dis_wgrad_pairs_workspace(int n, int hX, int wX, int hG, int wG, int cX, int cG, int ldX, int ldG, int k,
+                               int stride, int bf);
+int dis_wgrad_pairs_run(const float* X, int ldX, int xoff, int hX, int wX, int cX, int cX_w, const float* G, int ldG,
+                        int goff, int hG, int wG, int cG, int cG_w, float* grad_w, float* workspace, int n, int k,
+                        int stride, int pad, int bf, hipStream_t s);

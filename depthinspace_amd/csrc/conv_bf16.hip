@@ -14,11 +14,11 @@
 //   convb_wgrad_kernel<MTW, NTW, XB, GB>   weight gradient: split-K slabs over pixel ranges, fp32 MFMA on the values the
 //       bf16 tensors hold (exact products of bf16 values, fp32 accumulation), fp64 slab sums.
 //   element-wise helpers on bf16 nhwc tensors (activation gradient, channel copies, column sums).
-#include "common.h"
+#include "conv_args.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;
 
 #define CB_MAXTAPS 49
@@ -982,25 +982,12 @@ static void cb_launch(const GenArgsB& a, int bn, long grid, hipStream_t s) {
 
 // halo form: worth it when the image is large (tile quantisation of small maps wastes the tile; their layers are weight-bound
 // anyway) and the halo + weight buffers fit LDS.  Fills the halo fields of a.
-static int cb_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
-  return ncu;
-}
 static long cb_halo_lds(const GenArgsB& a, int bn);
 static bool cb_halo_plan(GenArgsB& a, int bn) {
   static const bool off = getenv("DIS_CONVB_HALO") && getenv("DIS_CONVB_HALO")[0] == '0';
   if (off || (long)a.hv * a.wv < 1024 || a.ntaps > CB_MAXTAPS) return false;
-  int dy0 = a.tdy[0], dy1 = a.tdy[0], dx0 = a.tdx[0], dx1 = a.tdx[0];
-  for (int t = 1; t < a.ntaps; ++t) {
-    dy0 = a.tdy[t] < dy0 ? a.tdy[t] : dy0; dy1 = a.tdy[t] > dy1 ? a.tdy[t] : dy1;
-    dx0 = a.tdx[t] < dx0 ? a.tdx[t] : dx0; dx1 = a.tdx[t] > dx1 ? a.tdx[t] : dx1;
-  }
+  const ConvTapBox box = conv_plan_tap_box(a);
+  const int dy0 = box.dy0, dy1 = box.dy1, dx0 = box.dx0, dx1 = box.dx1;
   a.dy0 = dy0; a.dx0 = dx0;
   a.trh = CBH_TR;
   a.HR = (a.trh - 1) * a.S + (dy1 - dy0) + 1;
@@ -1033,19 +1020,8 @@ static bool cb_halo_plan(GenArgsB& a, int bn) {
   }
   // column walk (convb_halo_kernel, KC): a full K x K stride-1 window on 16-row tiles, the instances that exist
   a.kc = 0;
-  {
-    const int K = dy1 - dy0 + 1;
-    static const bool nokc = getenv("DIS_CONVB_KC") && getenv("DIS_CONVB_KC")[0] == '0';
-    if (!nokc && a.nph == 1 && a.S == 1 && a.TP == 1 && !a.res && a.trh == 16 && dx1 - dx0 + 1 == K && a.ntaps == K * K &&
-        ((K == 7 && bn == 32) || (K == 5 && bn == 64))) {
-      const long wsz = 2L * K * 4 * bn * 16 / 2;   // two buffers of one column (16-bit words)
-      if (256 + 2 * wsz + (long)a.HR * a.HC * a.PS * 2 <= 150 * 1024) {
-        a.kc = K;
-        a.GT = K;
-        a.wsz16 = (int)wsz;
-      }
-    }
-  }
+  static const bool nokc = getenv("DIS_CONVB_KC") && getenv("DIS_CONVB_KC")[0] == '0';
+  if (!nokc) conv_plan_column_walk(a, box, bn, 4, 150 * 1024);
   return cb_halo_lds(a, bn) <= 150 * 1024;
 }
 static long cb_halo_lds(const GenArgsB& a, int bn) { return 256 + 2L * a.wsz16 + (long)a.HR * a.HC * a.PS * 2; }
@@ -1106,15 +1082,7 @@ static int cb_run_halo(GenArgsB a, int x_bf16, int y_bf16, int bn, const float* 
   p.w = w_raw; p.packed = wpack; p.ntaps = a.ntaps; p.nchunk = a.nchunk; p.nblk = a.nblk; p.bn = bn;
   p.ci_real = ci_real; p.co_real = co_real; p.tp = a.TP; p.nks = a.nks; p.s_ci = s_ci; p.s_co = s_co;
   for (int t = 0; t < a.ntaps; ++t) p.tsrc[t] = tsrc[t];
-  if (a.kc > 0) {
-    // column walk: taps ordered by (dx, dy) ascending - slot (dx - dx0) * kc + (dy - dy0); the window is full (cb_halo_plan)
-    short ty[CB_MAXTAPS], tx[CB_MAXTAPS];
-    for (int t = 0; t < a.ntaps; ++t) {
-      const int slot = (a.tdx[t] - a.dx0) * a.kc + (a.tdy[t] - a.dy0);
-      ty[slot] = a.tdy[t]; tx[slot] = a.tdx[t]; p.tsrc[slot] = tsrc[t];
-    }
-    for (int t = 0; t < a.ntaps; ++t) a.tdy[t] = ty[t], a.tdx[t] = tx[t];
-  }
+  if (a.kc > 0) conv_plan_column_order(a, tsrc, p.tsrc);
   const long ptotal = (long)a.nchunk * a.nblk * a.nks * 4 * bn * 8;
   if (w_raw) {  // (null: the call runs on weights dis_convb_pack_batch has packed)
     hipLaunchKernelGGL(convb_pack_halo_kernel, dim3(dis_ew_grid(ptotal, 256)), dim3(256), 0, s, p);
@@ -1124,12 +1092,7 @@ static int cb_run_halo(GenArgsB a, int x_bf16, int y_bf16, int bn, const float* 
   const long units = (long)a.n * a.tiles_y * a.tiles_x * a.nblk;
   if (units > 2147483647L) return DIS_ERR_BAD_SHAPE;
   const long lds = cb_halo_lds(a, bn);
-  // persistent grid: as many workgroups as stay resident (LDS-bound, at most 6 per CU), a multiple of the 8 XCDs
-  long wpc = (150L * 1024) / lds;
-  wpc = wpc > 6 ? 6 : (wpc < 1 ? 1 : wpc);
-  long grid = wpc * cb_num_cus();
-  if (grid > units) grid = units;
-  if (grid >= 8) grid -= grid % 8;
+  const long grid = conv_plan_persistent_grid(lds, 150L * 1024, 6, dis_num_cus(), units);   // (LDS-bound, at most 6 per CU)
   const int nh = (int)(((long)a.HR * a.HC * ((a.PS - 8) / 8) + 255) / 256);
   int rc;
   if (x_bf16 && y_bf16) rc = cbh_launch<true, true>(a, bn, nh, grid, lds, s);
@@ -1240,19 +1203,7 @@ extern "C" long dis_convb_splitk_workspace(int mode, int x_bf16, int n, int hin,
     const int ks = cb_ksplit(((M + bm - 1) / bm) * nblk, (int)(ntaps * nst));
     return ks > 1 ? (long)ks * M * nblk * bn : 0;
   };
-  const bool phased = (mode == DIS_CONVG_CONV_DGRAD || mode == DIS_CONVG_TCONV) && stride == 2;
-  if (!phased) return need(hout, wout, k * k);
-  long best = 0;
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      int nt = 0;
-      for (int ky = 0; ky < k; ++ky)
-        for (int kx = 0; kx < k; ++kx)
-          if (!((py + pad - ky) & 1) && !((px + pad - kx) & 1)) ++nt;
-      const long v = need((hout - py + 1) / 2, (wout - px + 1) / 2, nt);
-      best = v > best ? v : best;
-    }
-  return best;
+  return conv_plan_max_need(mode, k, stride, pad, hout, wout, need);
 }
 
 // workspace in 16-bit words for ONE phase
@@ -1262,8 +1213,6 @@ extern "C" long dis_convb_pack_workspace(int cin, int cout, int k) {
   const long nblk = (cout + bn - 1) / bn, nchunk = (cin + CB_CK - 1) / CB_CK;
   return (long)k * k * nchunk * nblk * 4 * bn * 8;
 }
-
-static int cb_floordiv2(int v) { return (v >= 0) ? v / 2 : -((-v + 1) / 2); }
 
 // Same modes and argument meaning as dis_convg_run (conv_gen.hip); ldx / xoff / ldy / yoff count ELEMENTS of the tensor's
 // own type; x_bf16 / y_bf16 select bf16 (1) or fp32 (0) storage of x / y.  bf16 tensors need ld, offset and cin that
@@ -1279,7 +1228,7 @@ extern "C" int dis_convb_run(int mode, const void* x, int x_bf16, int ldx, int x
   if (n <= 0 || hin <= 0 || win <= 0 || hout <= 0 || wout <= 0 || cin <= 0 || cout <= 0 || cin_w <= 0 || cout_w <= 0 ||
       k <= 0 || pad < 0)
     return DIS_ERR_BAD_SHAPE;
-  if (k * k > CB_MAXTAPS || (stride != 1 && stride != 2) || mode < 0 || mode > 3) return DIS_ERR_UNSUPPORTED;
+  if (!conv_plan_supported(mode, k, stride)) return DIS_ERR_UNSUPPORTED;
   const int xa = x_bf16 ? 7 : 3, ya = y_bf16 ? 3 : 0;
   if ((cin & xa) || (xoff & xa) || (ldx & xa) || xoff + cin > ldx || yoff + cout > ldy || cin_w > cin || cout_w > cout)
     return DIS_ERR_BAD_SHAPE;
@@ -1290,98 +1239,17 @@ extern "C" int dis_convb_run(int mode, const void* x, int x_bf16, int ldx, int x
   a.x = x; a.w = nullptr; a.bias = bias; a.y = y;
   a.n = n; a.hin = hin; a.win = win; a.ldx = ldx; a.xoff = xoff; a.cin = cin;
   a.hf = hout; a.wf = wout; a.ldy = ldy; a.yoff = yoff; a.cout = cout; a.act = act;
-  short tsrc[CB_MAXTAPS];
-  const long kk = (long)k * k;
   bf16_t* wp = (bf16_t*)wpack;
+  const long pstride = dis_convb_pack_workspace(cin, cout, k);   // every phase packs into its own slice
   // (split-K partial sums of the small maps: behind the four packing slices)
   a.ksplit = 1;
-  a.nph = 1;
   a.skcap = dis_convb_splitk_workspace(mode, x_bf16, n, hin, win, hout, wout, cin, cout, k, stride, pad);
-  a.skpart = a.skcap > 0 ? (float*)(wp + 4 * dis_convb_pack_workspace(cin, cout, k)) : nullptr;
-  if (mode == DIS_CONVG_CONV || mode == DIS_CONVG_TCONV_DGRAD) {
-    if (mode == DIS_CONVG_CONV) {
-      if (hout != (hin + 2 * pad - k) / stride + 1 || wout != (win + 2 * pad - k) / stride + 1) return DIS_ERR_BAD_SHAPE;
-    } else if (stride != 2) {
-      return DIS_ERR_UNSUPPORTED;
-    }
-    a.hv = hout; a.wv = wout; a.S = stride; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
-    a.ntaps = k * k;
-    for (int ky = 0; ky < k; ++ky)
-      for (int kx = 0; kx < k; ++kx) {
-        a.tdy[ky * k + kx] = (short)(ky - pad);
-        a.tdx[ky * k + kx] = (short)(kx - pad);
-        tsrc[ky * k + kx] = (short)(ky * k + kx);
-      }
-    return cb_run(a, x_bf16, y_bf16, w, wp, cin_w, cout_w, kk, (long)cin_w * kk, tsrc, s);
-  }
-  const long s_ci = (long)cout_w * kk, s_co = kk;
-  if (stride == 1) {
-    a.hv = hout; a.wv = wout; a.S = 1; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
-    a.ntaps = k * k;
-    for (int ky = 0; ky < k; ++ky)
-      for (int kx = 0; kx < k; ++kx) {
-        a.tdy[ky * k + kx] = (short)(pad - ky);
-        a.tdx[ky * k + kx] = (short)(pad - kx);
-        tsrc[ky * k + kx] = (short)(ky * k + kx);
-      }
-    return cb_run(a, x_bf16, y_bf16, w, wp, cin_w, cout_w, s_ci, s_co, tsrc, s);
-  }
-  const long pstride = dis_convb_pack_workspace(cin, cout, k);
+  a.skpart = a.skcap > 0 ? (float*)(wp + 4 * pstride) : nullptr;
   static const bool nofuse = getenv("DIS_CONVB_NO_FUSED_PHASES") != nullptr;
-  if (!nofuse && k * k <= 255) {
-    // the four parity classes in ONE launch of the halo kernel (they read the same input tile): taps listed class by class
-    GenArgsB b = a;
-    b.hv = (hout + 1) / 2; b.wv = (wout + 1) / 2; b.S = 1;
-    b.osy = 2; b.ooy = 0; b.osx = 2; b.oox = 0;
-    b.nph = 4;
-    int nt = 0;
-    bool ok = true;
-    for (int py = 0; py < 2; ++py)
-      for (int px = 0; px < 2; ++px) {
-        const int ph = py * 2 + px, t0 = nt;
-        for (int ky = 0; ky < k; ++ky) {
-          if ((py + pad - ky) & 1) continue;
-          for (int kx = 0; kx < k; ++kx) {
-            if ((px + pad - kx) & 1) continue;
-            b.tdy[nt] = (short)cb_floordiv2(py + pad - ky);
-            b.tdx[nt] = (short)cb_floordiv2(px + pad - kx);
-            tsrc[nt] = (short)(ky * k + kx);
-            ++nt;
-          }
-        }
-        b.ph_k0[ph] = (unsigned char)t0; b.ph_kn[ph] = (unsigned char)(nt - t0);
-        b.ph_oy[ph] = (unsigned char)py; b.ph_ox[ph] = (unsigned char)px;
-        ok = ok && nt > t0;
-      }
-    b.ntaps = nt;
-    if (ok) {
-      const int rc = cb_run(b, x_bf16, y_bf16, w, wp, cin_w, cout_w, s_ci, s_co, tsrc, s, true);
-      if (rc != DIS_ERR_UNSUPPORTED) return rc;
-    }
-  }
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      GenArgsB b = a;
-      b.hv = (hout - py + 1) / 2; b.wv = (wout - px + 1) / 2; b.S = 1;
-      b.osy = 2; b.ooy = py; b.osx = 2; b.oox = px;
-      int nt = 0;
-      for (int ky = 0; ky < k; ++ky) {
-        if ((py + pad - ky) & 1) continue;
-        for (int kx = 0; kx < k; ++kx) {
-          if ((px + pad - kx) & 1) continue;
-          b.tdy[nt] = (short)cb_floordiv2(py + pad - ky);
-          b.tdx[nt] = (short)cb_floordiv2(px + pad - kx);
-          tsrc[nt] = (short)(ky * k + kx);
-          ++nt;
-        }
-      }
-      b.ntaps = nt;
-      if (b.hv <= 0 || b.wv <= 0) continue;
-      if (nt == 0) return DIS_ERR_UNSUPPORTED;
-      int rc = cb_run(b, x_bf16, y_bf16, w, wp + (long)(py * 2 + px) * pstride, cin_w, cout_w, s_ci, s_co, tsrc, s);
-      if (rc != DIS_OK) return rc;
-    }
-  return DIS_OK;
+  return conv_plan_run(a, mode, k, stride, pad, hin, win, hout, wout, cin_w, cout_w, !nofuse,
+                       [&](const GenArgsB& b, int slice, long s_ci, long s_co, const short* tsrc, bool halo_only) {
+                         return cb_run(b, x_bf16, y_bf16, w, wp + slice * pstride, cin_w, cout_w, s_ci, s_co, tsrc, s, halo_only);
+                       });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1605,43 +1473,10 @@ static void cbh_launch(int c8, int blocks, const void* X, int ldX, int xoff, con
 #undef CBH_CASE
 }
 
-static void cbw_tiles(int cX, int cG, int* mtw, int* ntw) {
-  *mtw = cX > 32 ? 2 : 1;
-  *ntw = cG > 32 ? 2 : 1;
-}
-static void cbw_plan(int n, int hG, int wG, int cX, int cG, int k, int* nxb, int* ngb, int* nsplit, int* mper) {
-  int mtw, ntw;
-  cbw_tiles(cX, cG, &mtw, &ntw);
-  const int TX = 32 * mtw, TG = 32 * ntw;
-  *nxb = (cX + TX - 1) / TX;
-  *ngb = (cG + TG - 1) / TG;
-  const long base = (long)k * k * (*nxb) * (*ngb);
-  const long M = (long)n * hG * wG;
-  long sp = (2048 + base - 1) / base;
-  const long maxsp = (M + 255) / 256;
-  if (sp > maxsp) sp = maxsp;
-  if (sp < 1) sp = 1;
-  long mp = (M + sp - 1) / sp;
-  mp = (mp + 31) / 32 * 32;
-  sp = (M + mp - 1) / mp;
-  *nsplit = (int)sp;
-  *mper = (int)mp;
-}
-// bf16 x AND bf16 gy, >= 16 / 32 channels, 3x3 / 5x5 / 7x7 taps: the one-pass slice-pair kernel of conv2d.hip in its
-// bf16-input form (conv_wgrad_bf16x3_kernel<..., BF = true>: one bf16 MFMA product per MAC, operands fetched from the
-// [pixel][channel] LDS images with the transposing read)
-long dis_wgrad_pairs_workspace(int n, int hX, int wX, int hG, int wG, int cX, int cG, int ldX, int ldG, int k,
-                               int stride, int bf);
-int dis_wgrad_pairs_run(const float* X, int ldX, int xoff, int hX, int wX, int cX, int cX_w, const float* G, int ldG,
-                        int goff, int hG, int wG, int cG, int cG_w, float* grad_w, float* workspace, int n, int k,
-                        int stride, int pad, int bf, hipStream_t s);
-
 extern "C" long dis_convb_wgrad_workspace(int n, int hG, int wG, int cX, int cG, int k) {
   if (n <= 0 || hG <= 0 || wG <= 0 || cX <= 0 || cG <= 0 || k <= 0 || k * k > CB_MAXTAPS) return -1;
-  int nxb, ngb, nsplit, mper, mtw, ntw;
-  cbw_plan(n, hG, wG, cX, cG, k, &nxb, &ngb, &nsplit, &mper);
-  cbw_tiles(cX, cG, &mtw, &ntw);
-  const long f32 = (long)nsplit * k * k * (nxb * 32 * mtw) * (ngb * 32 * ntw);
+  const WgradSplitPlan p = wgrad_split_plan(n, hG, wG, cX, cG, k);
+  const long f32 = (long)p.nsplit * k * k * (p.nxb * 32 * p.mtw) * (p.ngb * 32 * p.ntw);
   // (the slice-pair form, if dis_convb_wgrad takes it for this layer: the stride is not known here, so size for both)
   const long b1 = dis_wgrad_pairs_workspace(n, 1, 1, hG, wG, cX, cG, 8, 8, k, 1, 1);
   const long b2 = dis_wgrad_pairs_workspace(n, 1, 1, hG, wG, cX, cG, 8, 8, k, 2, 1);
@@ -1691,9 +1526,9 @@ extern "C" int dis_convb_wgrad(const void* X, int x_bf16, int ldX, int xoff, int
   a.n = n; a.hX = hX; a.wX = wX; a.ldX = ldX; a.xoff = xoff; a.cX = cX;
   a.hG = hG; a.wG = wG; a.ldG = ldG; a.goff = goff; a.cG = cG;
   a.S = stride; a.pad = pad; a.k = k;
-  int nsplit, mtw, ntw;
-  cbw_plan(n, hG, wG, cX, cG, k, &a.nxb, &a.ngb, &nsplit, &a.mper);
-  cbw_tiles(cX, cG, &mtw, &ntw);
+  const WgradSplitPlan p = wgrad_split_plan(n, hG, wG, cX, cG, k);
+  const int nsplit = p.nsplit, mtw = p.mtw, ntw = p.ntw;
+  a.nxb = p.nxb; a.ngb = p.ngb; a.mper = p.mper;
   a.cXp = a.nxb * 32 * mtw;
   a.cGp = a.ngb * 32 * ntw;
   const dim3 grid((unsigned)(k * k * a.nxb * a.ngb), (unsigned)nsplit);

@@ -20,6 +20,7 @@
 //     tile (one tap) x TX x-channels x TG g-channels per workgroup, k = 32 pixels per step, split-K over
 //     pixel ranges into partial slabs that a second kernel sums in a fixed order (deterministic).
 #include "conv_args.h"
+#include "conv_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1246,16 +1247,6 @@ __global__ __launch_bounds__(256) void convh2_pack_kernel(PackH2Args a) {
   }
 }
 
-static int ch2_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-    if (ncu <= 0) ncu = 256;
-  }
-  return ncu;
-}
 static long ch2_lds(const GenArgs& a) { return 256 + 2L * a.wsz16 + (long)a.HR * a.HC * a.PS * 2; }
 #define CH2_LDS_MAX (156 * 1024)
 // halo form: worth it when the map is large (tile quantisation wastes small maps; their layers are weight-bound anyway) and the
@@ -1266,11 +1257,8 @@ static bool ch2_plan(GenArgs& a, int bn) {
   const char* mh = getenv("DIS_CONVG_HALO_MIN");
   const long min_hw = mh ? atol(mh) : 1024;
   if ((long)a.hv * a.wv < min_hw || a.ntaps > CG_MAXTAPS) return false;
-  int dy0 = a.tdy[0], dy1 = a.tdy[0], dx0 = a.tdx[0], dx1 = a.tdx[0];
-  for (int t = 1; t < a.ntaps; ++t) {
-    dy0 = a.tdy[t] < dy0 ? a.tdy[t] : dy0; dy1 = a.tdy[t] > dy1 ? a.tdy[t] : dy1;
-    dx0 = a.tdx[t] < dx0 ? a.tdx[t] : dx0; dx1 = a.tdx[t] > dx1 ? a.tdx[t] : dx1;
-  }
+  const ConvTapBox box = conv_plan_tap_box(a);
+  const int dy0 = box.dy0, dy1 = box.dy1, dx0 = box.dx0, dx1 = box.dx1;
   a.dy0 = dy0; a.dx0 = dx0;
   a.TP = a.cin <= 16 ? 2 : 1;
   if (a.nph > 1 && a.TP != 1) return false;   // (a k-step of two taps could straddle two phases)
@@ -1310,19 +1298,8 @@ static bool ch2_plan(GenArgs& a, int bn) {
   }
   // column walk (see convh2_kernel, KC): a full K x K stride-1 window, 16-row tiles, the instances that exist
   a.kc = 0;
-  {
-    const int K = dy1 - dy0 + 1;
-    static const bool nokc = getenv("DIS_CONVG_KC") && getenv("DIS_CONVG_KC")[0] == '0';
-    if (!nokc && a.nph == 1 && a.S == 1 && a.TP == 1 && !a.res && a.trh == 16 && dx1 - dx0 + 1 == K && a.ntaps == K * K &&
-        ((K == 7 && bn == 32) || (K == 5 && bn == 64))) {
-      const long wsz = 2L * K * 8 * bn * 16 / 2;   // two buffers of one column
-      if (256 + 2 * wsz + (long)a.HR * a.HC * a.PS * 2 <= CH2_LDS_MAX) {
-        a.kc = K;
-        a.GT = K;
-        a.wsz16 = (int)wsz;
-      }
-    }
-  }
+  static const bool nokc = getenv("DIS_CONVG_KC") && getenv("DIS_CONVG_KC")[0] == '0';
+  if (!nokc) conv_plan_column_walk(a, box, bn, 8, CH2_LDS_MAX);
   a.tiles_y = (a.hv + a.trh - 1) / a.trh;
   // weight groups (streamed form): GT k-steps each, cut at the phase boundaries
   int ng = 0;
@@ -1396,15 +1373,7 @@ static int ch2_run(GenArgs a, int bn, const float* w_raw, float* wpack, int ci_r
   p.w = w_raw; p.packed = (unsigned short*)wpack; p.ntaps = a.ntaps; p.nchunk = a.nchunk; p.nblk = a.nblk; p.bn = bn;
   p.ci_real = ci_real; p.co_real = co_real; p.tp = a.TP; p.nks = a.nks; p.s_ci = s_ci; p.s_co = s_co;
   for (int t = 0; t < a.ntaps; ++t) p.tsrc[t] = tsrc[t];
-  if (a.kc > 0) {
-    // column walk: taps ordered by (dx, dy) ascending - slot (dx - dx0) * kc + (dy - dy0); the window is full (ch2_plan)
-    short ty[CG_MAXTAPS], tx[CG_MAXTAPS];
-    for (int t = 0; t < a.ntaps; ++t) {
-      const int slot = (a.tdx[t] - a.dx0) * a.kc + (a.tdy[t] - a.dy0);
-      ty[slot] = a.tdy[t]; tx[slot] = a.tdx[t]; p.tsrc[slot] = tsrc[t];
-    }
-    for (int t = 0; t < a.ntaps; ++t) a.tdy[t] = ty[t], a.tdx[t] = tx[t];
-  }
+  if (a.kc > 0) conv_plan_column_order(a, tsrc, p.tsrc);
   p.ws = const_cast<float*>(a.f2ws); p.n = 0;   // (no per-image exponents: the halo kernel scales x per tile)
   const long ptotal = (long)a.nchunk * a.nblk * a.nks * 4 * bn * 4;
   hipLaunchKernelGGL(convh2_pack_kernel, dim3(dis_ew_grid(ptotal, 256)), dim3(256), 0, s, p);
@@ -1412,12 +1381,7 @@ static int ch2_run(GenArgs a, int bn, const float* w_raw, float* wpack, int ci_r
   const long units = (long)a.n * a.tiles_y * a.tiles_x * a.nblk;
   if (units > 2147483647L) return DIS_ERR_BAD_SHAPE;
   const long lds = ch2_lds(a);
-  // persistent grid: as many workgroups as stay resident (LDS-bound, at most 4 per CU), a multiple of the 8 XCDs
-  long wpc = (160L * 1024) / lds;
-  wpc = wpc > 4 ? 4 : (wpc < 1 ? 1 : wpc);
-  long grid = wpc * ch2_num_cus();
-  if (grid > units) grid = units;
-  if (grid >= 8) grid -= grid % 8;
+  const long grid = conv_plan_persistent_grid(lds, 160L * 1024, 4, dis_num_cus(), units);   // (LDS-bound, at most 4 per CU)
   const int nh = (int)(((long)a.HR * a.HC * (a.PL / 4) + 255) / 256);
   int rc;
   if (bn == 64) rc = ch2_launch<64>(a, nh, grid, lds, s);
@@ -1592,19 +1556,7 @@ extern "C" long dis_convg_splitk_workspace(int mode, int n, int hin, int win, in
     const int ks = cg2_ksplit(((M + bm - 1) / bm) * nblk, (int)(ntaps * nchunk));
     return ks > 1 ? (long)ks * M * nblk * bn : 0;
   };
-  const bool phased = (mode == DIS_CONVG_CONV_DGRAD || mode == DIS_CONVG_TCONV) && stride == 2;
-  if (!phased) return need(hout, wout, k * k);
-  long best = 0;
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      int nt = 0;
-      for (int ky = 0; ky < k; ++ky)
-        for (int kx = 0; kx < k; ++kx)
-          if (!((py + pad - ky) & 1) && !((px + pad - kx) & 1)) ++nt;
-      const long v = need((hout - py + 1) / 2, (wout - px + 1) / 2, nt);
-      best = v > best ? v : best;
-    }
-  return best;
+  return conv_plan_max_need(mode, k, stride, pad, hout, wout, need);
 }
 
 extern "C" long dis_convg_pack_workspace(int cin, int cout, int k) {
@@ -1616,15 +1568,6 @@ extern "C" long dis_convg_pack_workspace(int cin, int cout, int k) {
   return (f32 > b3 ? f32 : b3) + CG2_WS;   // (+ the block-scale workspace of the two-term fp16 form, at the end of the first slice)
 }
 
-static int floordiv2(int v) { return (v >= 0) ? v / 2 : -((-v + 1) / 2); }
-
-// conv2d.hip: 3x3 stride-1 layers as 32 x 32 channel-slice launches of the halo-resident bf16x3 kernel
-long dis_bx_slices_ok(int n, int h, int wd, int cin, int cout, int ldx, int ldy, int xoff, int yoff, int k, int stride,
-                      int pad, int act);
-int dis_bx_slices_run(int dgrad, const float* x, int ldx, int xoff, int cin, int cin_w, const float* w,
-                      const float* bias, float* y, int ldy, int yoff, int cout, int cout_w, int n, int h, int wd, int k,
-                      int act, hipStream_t stream);
-
 extern "C" int dis_convg_run(int mode, const float* x, int ldx, int xoff, const float* w, const float* bias,
                              float* y, int ldy, int yoff, float* wpack, int n, int hin, int win, int cin,
                              int cin_w, int hout, int wout, int cout, int cout_w, int k, int stride, int pad,
@@ -1633,7 +1576,7 @@ extern "C" int dis_convg_run(int mode, const float* x, int ldx, int xoff, const 
   if (n <= 0 || hin <= 0 || win <= 0 || hout <= 0 || wout <= 0 || cin <= 0 || cout <= 0 || cin_w <= 0 ||
       cout_w <= 0 || k <= 0 || pad < 0)
     return DIS_ERR_BAD_SHAPE;
-  if (k * k > CG_MAXTAPS || (stride != 1 && stride != 2) || mode < 0 || mode > 3) return DIS_ERR_UNSUPPORTED;
+  if (!conv_plan_supported(mode, k, stride)) return DIS_ERR_UNSUPPORTED;
   if ((cin & 3) || (xoff & 3) || (ldx & 3) || xoff + cin > ldx || yoff + cout > ldy || cin_w > cin || cout_w > cout)
     return DIS_ERR_BAD_SHAPE;
   hipStream_t s = (hipStream_t)stream;
@@ -1648,115 +1591,27 @@ extern "C" int dis_convg_run(int mode, const float* x, int ldx, int xoff, const 
   a.x = x; a.w = nullptr; a.bias = bias; a.y = y;
   a.n = n; a.hin = hin; a.win = win; a.ldx = ldx; a.xoff = xoff; a.cin = cin;
   a.hf = hout; a.wf = wout; a.ldy = ldy; a.yoff = yoff; a.cout = cout; a.act = act;
-  short tsrc[CG_MAXTAPS];
   const long kk = (long)k * k;
-  a.f2ws = nullptr; a.ksplit = 1; a.skpart = nullptr; a.skcap = 0; a.nph = 1;
+  a.f2ws = nullptr; a.ksplit = 1; a.skpart = nullptr; a.skcap = 0;
   F2Maxima mxv = {};
-  F2Maxima* mx = &mxv;
+  const long pstride = dis_convg_pack_workspace(cin, cout, k);  // every phase packs into its own slice
   if (dis_f2_enabled() && cin >= CG3_CK && n <= CG2_NMAX) {
     // (split-K partial sums: behind the packing slices, dis_convg_splitk_workspace floats)
-    const int phases = ((mode == DIS_CONVG_CONV_DGRAD || mode == DIS_CONVG_TCONV) && stride == 2) ? 4 : 1;
+    const int phases = conv_plan_phased(mode, stride) ? 4 : 1;
     a.skcap = dis_convg_splitk_workspace(mode, n, hin, win, hout, wout, cin, cout, k, stride, pad);
-    a.skpart = a.skcap > 0 ? wpack + dis_convg_pack_workspace(cin, cout, k) * phases : nullptr;
+    a.skpart = a.skcap > 0 ? wpack + pstride * phases : nullptr;
     // two-term fp16 form: block maxima of this call's x (per sample) and weights, one launch in front of the packing launch(es)
-    float* f2ws = wpack + dis_convg_pack_workspace(cin, cout, k) - CG2_WS;
+    float* f2ws = wpack + pstride - CG2_WS;
     mxv.x = x; mxv.n = n; mxv.hw = (long)hin * win; mxv.ldx = ldx; mxv.xoff = xoff; mxv.cin = cin;
     mxv.w = w; mxv.wcount = (long)cin_w * cout_w * kk; mxv.ws = f2ws;
     a.f2ws = f2ws;
   }
-  if (mode == DIS_CONVG_CONV || mode == DIS_CONVG_TCONV_DGRAD) {
-    // direct form: out[vy][vx] = sum_taps in[vy*S + ky - pad][vx*S + kx - pad] * W
-    if (mode == DIS_CONVG_CONV) {
-      if (hout != (hin + 2 * pad - k) / stride + 1 || wout != (win + 2 * pad - k) / stride + 1) return DIS_ERR_BAD_SHAPE;
-    } else if (stride != 2) {
-      return DIS_ERR_UNSUPPORTED;
-    }
-    a.hv = hout; a.wv = wout; a.S = stride; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
-    a.ntaps = k * k;
-    for (int ky = 0; ky < k; ++ky)
-      for (int kx = 0; kx < k; ++kx) {
-        a.tdy[ky * k + kx] = (short)(ky - pad);
-        a.tdx[ky * k + kx] = (short)(kx - pad);
-        tsrc[ky * k + kx] = (short)(ky * k + kx);
-      }
-    // conv: w[co][ci][ky][kx] (co rows of cin_w);  tconv dgrad: w[ci_t = out][co_t = in][ky][kx]
-    const long s_ci = kk, s_co = (long)cin_w * kk;
-    return cg_run(a, w, wpack, cin_w, cout_w, s_ci, s_co, tsrc, s, mx);
-  }
-  // transposed form: out[oy][ox] = sum_{ky,kx : parity} in[(oy + pad - ky)/S][(ox + pad - kx)/S] * W
-  //   conv dgrad:  w[ci_in(= conv cout)][co_out(= conv cin)]  stored as w[conv_co][conv_ci][ky][kx]
-  //   tconv fwd :  w[ci][co][ky][kx]
-  // both: in-channel stride = cout_w*k*k, out-channel stride = k*k
-  const long s_ci = (long)cout_w * kk, s_co = kk;
-  if (stride == 1) {
-    a.hv = hout; a.wv = wout; a.S = 1; a.osy = 1; a.ooy = 0; a.osx = 1; a.oox = 0;
-    a.ntaps = k * k;
-    for (int ky = 0; ky < k; ++ky)
-      for (int kx = 0; kx < k; ++kx) {
-        a.tdy[ky * k + kx] = (short)(pad - ky);
-        a.tdx[ky * k + kx] = (short)(pad - kx);
-        tsrc[ky * k + kx] = (short)(ky * k + kx);
-      }
-    return cg_run(a, w, wpack, cin_w, cout_w, s_ci, s_co, tsrc, s, mx);
-  }
-  const long pstride = dis_convg_pack_workspace(cin, cout, k);  // every phase packs into its own slice
-  if (a.f2ws && k * k <= 255 && !getenv("DIS_CONVG_NO_FUSED_PHASES")) {
-    // the four parity classes in ONE launch of the halo kernel (they read the same input tile): taps listed class by class
-    GenArgs b = a;
-    b.hv = (hout + 1) / 2; b.wv = (wout + 1) / 2; b.S = 1;
-    b.osy = 2; b.ooy = 0; b.osx = 2; b.oox = 0;
-    b.nph = 4;
-    int nt = 0;
-    bool ok = true;
-    for (int py = 0; py < 2; ++py)
-      for (int px = 0; px < 2; ++px) {
-        const int ph = py * 2 + px, t0 = nt;
-        for (int ky = 0; ky < k; ++ky) {
-          if ((py + pad - ky) & 1) continue;
-          for (int kx = 0; kx < k; ++kx) {
-            if ((px + pad - kx) & 1) continue;
-            b.tdy[nt] = (short)floordiv2(py + pad - ky);
-            b.tdx[nt] = (short)floordiv2(px + pad - kx);
-            tsrc[nt] = (short)(ky * k + kx);
-            ++nt;
-          }
-        }
-        b.ph_k0[ph] = (unsigned char)t0; b.ph_kn[ph] = (unsigned char)(nt - t0);
-        b.ph_oy[ph] = (unsigned char)py; b.ph_ox[ph] = (unsigned char)px;
-        ok = ok && nt > t0;
-      }
-    b.ntaps = nt;
-    if (ok) {
-      const int rc = cg_run(b, w, wpack, cin_w, cout_w, s_ci, s_co, tsrc, s, mx, true);
-      if (rc != DIS_ERR_UNSUPPORTED) return rc;
-    }
-  }
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      GenArgs b = a;
-      b.hv = (hout - py + 1) / 2; b.wv = (wout - px + 1) / 2; b.S = 1;
-      b.osy = 2; b.ooy = py; b.osx = 2; b.oox = px;
-      int nt = 0;
-      for (int ky = 0; ky < k; ++ky) {
-        if ((py + pad - ky) & 1) continue;
-        for (int kx = 0; kx < k; ++kx) {
-          if ((px + pad - kx) & 1) continue;
-          b.tdy[nt] = (short)floordiv2(py + pad - ky);
-          b.tdx[nt] = (short)floordiv2(px + pad - kx);
-          tsrc[nt] = (short)(ky * k + kx);
-          ++nt;
-        }
-      }
-      b.ntaps = nt;
-      if (b.hv <= 0 || b.wv <= 0) continue;
-      if (nt == 0) {
-        // no tap reaches this parity class (cannot happen for k >= 2): outputs would be bias only
-        return DIS_ERR_UNSUPPORTED;
-      }
-      int rc = cg_run(b, w, wpack + (long)(py * 2 + px) * pstride, cin_w, cout_w, s_ci, s_co, tsrc, s, mx);
-      if (rc != DIS_OK) return rc;
-    }
-  return DIS_OK;
+  // (the four parity classes in one launch: the two-term halo kernel only)
+  const bool try_fused = a.f2ws && conv_plan_phased(mode, stride) && !getenv("DIS_CONVG_NO_FUSED_PHASES");
+  return conv_plan_run(a, mode, k, stride, pad, hin, win, hout, wout, cin_w, cout_w, try_fused,
+                       [&](const GenArgs& b, int slice, long s_ci, long s_co, const short* tsrc, bool halo_only) {
+                         return cg_run(b, w, wpack + slice * pstride, cin_w, cout_w, s_ci, s_co, tsrc, s, &mxv, halo_only);
+                       });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1900,37 +1755,6 @@ __global__ void convg_wgrad_reduce_kernel(const float* __restrict__ part, float*
   }
 }
 
-static void wg_tiles(int cX, int cG, int* mtw, int* ntw) {
-  *mtw = cX > 32 ? 2 : 1;
-  *ntw = cG > 32 ? 2 : 1;
-}
-static void wg_plan(int n, int hG, int wG, int cX, int cG, int k, int* nxb, int* ngb, int* nsplit, int* mper) {
-  int mtw, ntw;
-  wg_tiles(cX, cG, &mtw, &ntw);
-  const int TX = 32 * mtw, TG = 32 * ntw;
-  *nxb = (cX + TX - 1) / TX;
-  *ngb = (cG + TG - 1) / TG;
-  const long base = (long)k * k * (*nxb) * (*ngb);
-  const long M = (long)n * hG * wG;
-  long sp = (2048 + base - 1) / base;
-  const long maxsp = (M + 255) / 256;  // at least 256 pixels (8 k-steps) per split
-  if (sp > maxsp) sp = maxsp;
-  if (sp < 1) sp = 1;
-  long mp = (M + sp - 1) / sp;
-  mp = (mp + 31) / 32 * 32;
-  sp = (M + mp - 1) / mp;
-  *nsplit = (int)sp;
-  *mper = (int)mp;
-}
-
-// conv2d.hip: layers with >= 32 channels on both sides and 3x3 / 5x5 taps run as 32 x 32 channel-slice pairs on the
-// one-pass bf16x3 kernel (x halo and gy tile staged once for all taps, accumulators in registers)
-long dis_wgrad_pairs_workspace(int n, int hX, int wX, int hG, int wG, int cX, int cG, int ldX, int ldG, int k,
-                               int stride, int bf);
-int dis_wgrad_pairs_run(const float* X, int ldX, int xoff, int hX, int wX, int cX, int cX_w, const float* G, int ldG,
-                        int goff, int hG, int wG, int cG, int cG_w, float* grad_w, float* workspace, int n, int k,
-                        int stride, int pad, int bf, hipStream_t s);
-
 // ---- weight gradient of a disparity head: ONE gradient channel (cG_w = 1), 3x3, stride 1 (fp32 twin of conv_bf16.hip's
 // convb_head_wgrad_kernel) ----
 // dW[tap][c] = sum_o x[o + tap - pad][c] * g[o] is a reduction with 9 cX outputs: no matrix core needed, HBM-bound on the ONE read
@@ -2006,10 +1830,8 @@ static bool cgh_eligible(int cX, int cG, int cG_w, int k, int stride, int hX, in
 
 extern "C" long dis_convg_wgrad_workspace(int n, int hG, int wG, int cX, int cG, int k) {
   if (n <= 0 || hG <= 0 || wG <= 0 || cX <= 0 || cG <= 0 || k <= 0 || k * k > CG_MAXTAPS) return -1;
-  int nxb, ngb, nsplit, mper, mtw, ntw;
-  wg_plan(n, hG, wG, cX, cG, k, &nxb, &ngb, &nsplit, &mper);
-  wg_tiles(cX, cG, &mtw, &ntw);
-  const long f32 = (long)nsplit * k * k * (nxb * 32 * mtw) * (ngb * 32 * ntw);
+  const WgradSplitPlan p = wgrad_split_plan(n, hG, wG, cX, cG, k);
+  const long f32 = (long)p.nsplit * k * k * (p.nxb * 32 * p.mtw) * (p.ngb * 32 * p.ntw);
   // (the slice-pair form, if dis_convg_wgrad takes it for this layer: the stride is not known here, so size for both)
   const long b1 = dis_wgrad_pairs_workspace(n, 1, 1, hG, wG, cX, cG, 4, 4, k, 1, 0);
   const long b2 = dis_wgrad_pairs_workspace(n, 1, 1, hG, wG, cX, cG, 4, 4, k, 2, 0);
@@ -2054,9 +1876,9 @@ extern "C" int dis_convg_wgrad(const float* X, int ldX, int xoff, int hX, int wX
   a.n = n; a.hX = hX; a.wX = wX; a.ldX = ldX; a.xoff = xoff; a.cX = cX;
   a.hG = hG; a.wG = wG; a.ldG = ldG; a.goff = goff; a.cG = cG;
   a.S = stride; a.pad = pad; a.k = k;
-  int nsplit, mtw, ntw;
-  wg_plan(n, hG, wG, cX, cG, k, &a.nxb, &a.ngb, &nsplit, &a.mper);
-  wg_tiles(cX, cG, &mtw, &ntw);
+  const WgradSplitPlan p = wgrad_split_plan(n, hG, wG, cX, cG, k);
+  const int nsplit = p.nsplit, mtw = p.mtw, ntw = p.ntw;
+  a.nxb = p.nxb; a.ngb = p.ngb; a.mper = p.mper;
   a.cXp = a.nxb * 32 * mtw;
   a.cGp = a.ngb * 32 * ntw;
   const dim3 grid((unsigned)(k * k * a.nxb * a.ngb), (unsigned)nsplit);

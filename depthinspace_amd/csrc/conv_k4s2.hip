@@ -256,16 +256,6 @@ hipError_t dis_k4s2_fwd_launch(const float* x, const float* w_oihw, const float*
   return hipSuccess;
 }
 
-static int k4_num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
 bool dis_f2_enabled();   // conv_f16x2.hip: the process-wide operand split (dis_set_conv_split)
 
 /* y = act(conv2d(x, w, stride 2, pad 1) + bias) for FuseNet's 4 x 4 down convolution, 32 -> 32 channels, w OIHW (32, 32, 4, 4) as the
@@ -279,7 +269,7 @@ extern "C" int dis_conv2d_fwd_k4s2_f16x2(const float* x, const float* w_oihw, co
   if (act < 0 || act > DIS_ACT_RELU) return DIS_ERR_UNSUPPORTED;
   if (!dis_f2_enabled()) return DIS_ERR_UNSUPPORTED;
   if ((long)hin * win * 128 >= 0x7fff0000L) return DIS_ERR_UNSUPPORTED;   // (31-bit byte offsets inside a sample)
-  hipError_t e = dis_k4s2_fwd_launch(x, w_oihw, bias, y, stats, n, hin, win, act, k4_num_cus(), (hipStream_t)stream);
+  hipError_t e = dis_k4s2_fwd_launch(x, w_oihw, bias, y, stats, n, hin, win, act, dis_num_cus(), (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   DIS_CHECK_LAUNCH();
   return DIS_OK;
@@ -476,7 +466,7 @@ extern "C" int dis_conv2d_dgrad_k4s2_f16x2(const float* gy, const float* w_oihw,
     attr_set = true;
   }
   const long ntiles = (long)n * ((a.hout + K4D_TR - 1) / K4D_TR) * ((a.wout + K4_TC - 1) / K4_TC);
-  long grid = 2L * k4_num_cus();
+  long grid = 2L * dis_num_cus();
   if (grid > ntiles) grid = ntiles;
   if (grid >= 8) grid -= grid % 8;
   if (grid < 1) grid = 1;

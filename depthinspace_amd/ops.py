@@ -1971,6 +1971,31 @@ def _colsum(G, c_real, out=None):
     return out
 
 
+def _conv_stream_shapes(name, x, weight, stride, pad, transposed, out_hw, out, dtype, cmult):
+    """Shapes of a _ConvG / _ConvB forward and its output y of storage type `dtype` (cout a multiple of cmult): a new tensor, or
+    the ConcatBuf slot `out` = (buffer, channel offset, channels).  -> (n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y)"""
+    n, hin, win, cin_mem = x.shape
+    if transposed:
+        cin_w, cout, k, _ = weight.shape
+        hout, wout = out_hw
+        if stride != 2 or hout > 2 * hin or wout > 2 * win:
+            raise RuntimeError('transposed conv: stride 2 and out_hw <= 2x input expected')
+    else:
+        cout, cin_w, k, _ = weight.shape
+        hout, wout = (hin + 2 * pad - k) // stride + 1, (win + 2 * pad - k) // stride + 1
+    fp32 = dtype == torch.float32   # (bf16 storage: _chk_act has checked x; its buffers are told apart from fp32 ones by dtype)
+    if (fp32 and cin_mem % 4) or cin_w > cin_mem or cout % cmult:
+        raise RuntimeError(f'{name}: bad channel counts cin_mem={cin_mem} cin_w={cin_w} cout={cout}')
+    if out is None:
+        y = torch.empty((n, hout, wout, cout), dtype=dtype, device=x.device)
+    else:
+        buf, off, c = out
+        if c != cout or tuple(buf.shape[:3]) != (n, hout, wout) or (not fp32 and buf.dtype != dtype):
+            raise RuntimeError(f'{name}: out slot {tuple(buf.shape)}[{off}:{off + c}] does not fit ({n},{hout},{wout},{cout})')
+        y = buf[..., off:off + c]
+    return n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y
+
+
 class _ConvG(torch.autograd.Function):
     """Conv2d / ConvTranspose2d(k,s2,p,op=1, cropped to out_hw) + bias + activation on nhwc tensors.
     x (n,h,w,cin_mem): cin_mem % 4 == 0 and >= the weight's input channels (extra channels must be zero-weight
@@ -1982,24 +2007,8 @@ class _ConvG(torch.autograd.Function):
         _chk(weight, bias)
         if not x.is_cuda or x.dtype != torch.float32:
             raise RuntimeError('depthinspace_amd ops need float32 CUDA(HIP) tensors: the HIP path is the only path')
-        n, hin, win, cin_mem = x.shape
-        if transposed:
-            cin_w, cout, k, _ = weight.shape
-            hout, wout = out_hw
-            if stride != 2 or hout > 2 * hin or wout > 2 * win:
-                raise RuntimeError('transposed conv: stride 2 and out_hw <= 2x input expected')
-        else:
-            cout, cin_w, k, _ = weight.shape
-            hout, wout = (hin + 2 * pad - k) // stride + 1, (win + 2 * pad - k) // stride + 1
-        if cin_mem % 4 or cin_w > cin_mem or cout % 4:
-            raise RuntimeError(f'convg: bad channel counts cin_mem={cin_mem} cin_w={cin_w} cout={cout}')
-        if out is None:
-            y = torch.empty((n, hout, wout, cout), dtype=torch.float32, device=x.device)
-        else:  # write into a ConcatBuf slot: (buffer, channel offset, channels)
-            buf, off, c = out
-            if c != cout or tuple(buf.shape[:3]) != (n, hout, wout):
-                raise RuntimeError(f'convg: out slot {tuple(buf.shape)}[{off}:{off + c}] does not fit ({n},{hout},{wout},{cout})')
-            y = buf[..., off:off + c]
+        n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y = _conv_stream_shapes(
+            'convg', x, weight, stride, pad, transposed, out_hw, out, torch.float32, 4)
         _convg_run(CONVG_TCONV if transposed else CONVG_CONV, x, weight, bias, y, n, hin, win, cin_mem, cin_w, hout,
                    wout, cout, cout, k, stride, pad, act)
         ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
@@ -2077,6 +2086,36 @@ def convg_transposed(x, weight, bias, out_hw, pad=1, act=ACT_NONE, out=None, dty
     return _ConvG.apply(x, weight, bias, 2, pad, act, True, tuple(out_hw), True, out)
 
 
+def _head_stream_fwd(ctx, run, x, weight, bias, alpha, offset):
+    """A disparity head as a one-channel streaming conv (run: _convg_run / _convb_run) + alpha*sigmoid(. - offset); y is float32"""
+    n, h, w, cin = x.shape
+    k = weight.shape[2]
+    y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+    run(CONVG_CONV, x, weight, bias, y.view(n, h, w, 1), n, h, w, cin, weight.shape[1], h, w, 1, 1, k, 1, k // 2, ACT_NONE)
+    lib.call('dis_sigmoid_affine_fwd', y, y, float(alpha), float(offset), y.numel())
+    ctx.save_for_backward(x, weight, y)
+    ctx.alpha = float(alpha)
+    ctx.bias_ref = bias
+    return y
+
+
+def _head_stream_bwd(ctx, run, wgrad, gy):
+    x, weight, y = ctx.saved_tensors
+    n, h, w, cin = x.shape
+    k = weight.shape[2]
+    cin_w = weight.shape[1]
+    gpre4 = torch.empty((n, h, w, 4), dtype=torch.float32, device=x.device)
+    lib.call('dis_sigmoid_affine_bwd', y, _c(gy), gpre4, ctx.alpha, n * h * w)
+    gx = torch.empty_like(x)
+    run(CONVG_CONV_DGRAD, gpre4, weight, None, gx, n, h, w, 4, 1, h, w, cin, cin_w, k, 1, k // 2, ACT_NONE)
+    gw, gw_ret = _sink(weight)
+    gb, gb_ret = _sink(ctx.bias_ref)
+    wgrad(x, h, w, cin, cin_w, gpre4, h, w, 4, 1, gw, n, k, 1, k // 2)
+    _colsum(gpre4, 1, out=gb)
+    _sinks_written()
+    return gx, gw_ret, gb_ret, None, None
+
+
 class _HeadG(torch.autograd.Function):
     """Conv2d(cin,1,3,pad 1) + alpha*sigmoid(. - offset) for any cin % 4 == 0: x nhwc -> y planar (n,1,h,w)."""
 
@@ -2085,40 +2124,27 @@ class _HeadG(torch.autograd.Function):
         x, weight, bias = _c(x), _c(weight), _c(bias)
         _chk(x, weight, bias)
         n, h, w, cin = x.shape
-        k = weight.shape[2]
-        y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
-        ctx.direct = k == 3 and cin in (16, 32) and weight.shape[1] == cin  # the one-pass head kernels (16 / 32 channels)
+        ctx.direct = weight.shape[2] == 3 and cin in (16, 32) and weight.shape[1] == cin  # the one-pass head kernels (16 / 32 channels)
         if ctx.direct:
+            y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
             lib.call('dis_disp_head_fwd', x, weight, bias, y, n, h, w, cin, float(alpha), float(offset))
-        else:
-            _convg_run(CONVG_CONV, x, weight, bias, y.view(n, h, w, 1), n, h, w, cin, weight.shape[1], h, w, 1, 1, k, 1,
-                       k // 2, ACT_NONE)
-            lib.call('dis_sigmoid_affine_fwd', y, y, float(alpha), float(offset), y.numel())
-        ctx.save_for_backward(x, weight, y)
-        ctx.alpha = float(alpha)
-        ctx.bias_ref = bias
-        return y
+            ctx.save_for_backward(x, weight, y)
+            ctx.alpha = float(alpha)
+            ctx.bias_ref = bias
+            return y
+        return _head_stream_fwd(ctx, _convg_run, x, weight, bias, alpha, offset)
 
     @staticmethod
     def backward(ctx, gy):
+        if not ctx.direct:
+            return _head_stream_bwd(ctx, _convg_run, _convg_wgrad, gy)
         x, weight, y = ctx.saved_tensors
         n, h, w, cin = x.shape
-        k = weight.shape[2]
-        cin_w = weight.shape[1]
         gw, gw_ret = _sink(weight)
         gb, gb_ret = _sink(ctx.bias_ref)
-        if ctx.direct:
-            gx = torch.empty_like(x)
-            ws = torch.empty(lib.fn('dis_disp_head_bwd_workspace')(n, h, w, cin), dtype=torch.float32, device=x.device)
-            lib.call('dis_disp_head_bwd', x, weight, y, _c(gy), gx, gw, gb, ws, n, h, w, cin, ctx.alpha)
-            _sinks_written()
-            return gx, gw_ret, gb_ret, None, None
-        gpre4 = torch.empty((n, h, w, 4), dtype=torch.float32, device=x.device)
-        lib.call('dis_sigmoid_affine_bwd', y, _c(gy), gpre4, ctx.alpha, n * h * w)
         gx = torch.empty_like(x)
-        _convg_run(CONVG_CONV_DGRAD, gpre4, weight, None, gx, n, h, w, 4, 1, h, w, cin, cin_w, k, 1, k // 2, ACT_NONE)
-        _convg_wgrad(x, h, w, cin, cin_w, gpre4, h, w, 4, 1, gw, n, k, 1, k // 2)
-        _colsum(gpre4, 1, out=gb)
+        ws = torch.empty(lib.fn('dis_disp_head_bwd_workspace')(n, h, w, cin), dtype=torch.float32, device=x.device)
+        lib.call('dis_disp_head_bwd', x, weight, y, _c(gy), gx, gw, gb, ws, n, h, w, cin, ctx.alpha)
         _sinks_written()
         return gx, gw_ret, gb_ret, None, None
 
@@ -2191,24 +2217,8 @@ class _ConvB(torch.autograd.Function):
         x, weight = _nhwc(x), _c(weight)
         _chk(weight, bias)
         _chk_act(x)
-        n, hin, win, cin_mem = x.shape
-        if transposed:
-            cin_w, cout, k, _ = weight.shape
-            hout, wout = out_hw
-            if stride != 2 or hout > 2 * hin or wout > 2 * win:
-                raise RuntimeError('transposed conv: stride 2 and out_hw <= 2x input expected')
-        else:
-            cout, cin_w, k, _ = weight.shape
-            hout, wout = (hin + 2 * pad - k) // stride + 1, (win + 2 * pad - k) // stride + 1
-        if cin_w > cin_mem or cout % 8:
-            raise RuntimeError(f'convb: bad channel counts cin_mem={cin_mem} cin_w={cin_w} cout={cout}')
-        if out is None:
-            y = torch.empty((n, hout, wout, cout), dtype=BF16, device=x.device)
-        else:
-            buf, off, c = out
-            if c != cout or tuple(buf.shape[:3]) != (n, hout, wout) or buf.dtype != BF16:
-                raise RuntimeError(f'convb: out slot {tuple(buf.shape)}[{off}:{off + c}] does not fit ({n},{hout},{wout},{cout})')
-            y = buf[..., off:off + c]
+        n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y = _conv_stream_shapes(
+            'convb', x, weight, stride, pad, transposed, out_hw, out, BF16, 8)
         _convb_run(CONVG_TCONV if transposed else CONVG_CONV, x, weight, bias, y, n, hin, win, cin_mem, cin_w, hout, wout,
                    cout, cout, k, stride, pad, act)
         ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
@@ -2277,33 +2287,11 @@ class _HeadB(torch.autograd.Function):
         x, weight, bias = _c(x), _c(weight), _c(bias)
         _chk(weight, bias)
         _chk_act(x)
-        n, h, w, cin = x.shape
-        k = weight.shape[2]
-        y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
-        _convb_run(CONVG_CONV, x, weight, bias, y.view(n, h, w, 1), n, h, w, cin, weight.shape[1], h, w, 1, 1, k, 1, k // 2,
-                   ACT_NONE)
-        lib.call('dis_sigmoid_affine_fwd', y, y, float(alpha), float(offset), y.numel())
-        ctx.save_for_backward(x, weight, y)
-        ctx.alpha = float(alpha)
-        ctx.bias_ref = bias
-        return y
+        return _head_stream_fwd(ctx, _convb_run, x, weight, bias, alpha, offset)
 
     @staticmethod
     def backward(ctx, gy):
-        x, weight, y = ctx.saved_tensors
-        n, h, w, cin = x.shape
-        k = weight.shape[2]
-        cin_w = weight.shape[1]
-        gpre4 = torch.empty((n, h, w, 4), dtype=torch.float32, device=x.device)
-        lib.call('dis_sigmoid_affine_bwd', y, _c(gy), gpre4, ctx.alpha, n * h * w)
-        gx = torch.empty_like(x)
-        _convb_run(CONVG_CONV_DGRAD, gpre4, weight, None, gx, n, h, w, 4, 1, h, w, cin, cin_w, k, 1, k // 2, ACT_NONE)
-        gw, gw_ret = _sink(weight)
-        gb, gb_ret = _sink(ctx.bias_ref)
-        _convb_wgrad(x, h, w, cin, cin_w, gpre4, h, w, 4, 1, gw, n, k, 1, k // 2)
-        _colsum(gpre4, 1, out=gb)
-        _sinks_written()
-        return gx, gw_ret, gb_ret, None, None
+        return _head_stream_bwd(ctx, _convb_run, _convb_wgrad, gy)
 
 
 class _WriteChannelsB(torch.autograd.Function):
