@@ -4,7 +4,8 @@ The reference writes one directory per track (`data/create_syn_data.py:245-255` 
 R / t [/ sgm_disp]; the LiteFlowNet presave writes flow.hdf5 with flow_ij; `data/presave_disp.py:116-117` writes
 single_frame_disp.hdf5 / multi_frame_disp.hdf5 with disp) plus `settings.pkl` (`create_syn_data.py:327-337`: imsize, pattern,
 baseline, K) and reads them back in `data/dataset.py:90-125`.  `TrackNpzDataset` (dataset.py here) reads the same datasets from
-.npz files; this module copies them over, dataset by dataset, without touching the values.
+.npz files; this module copies them over, dataset by dataset, without touching the values.  A track that arrives without flow.hdf5
+gets its flow.npz from `data/presave_flow.py`, one without sgm_disp from `data/presave_sgm.py`.
 
 h5py is not part of this image: `open_h5` is any callable path -> context manager of a mapping name -> array-like (h5py.File
 in real use, a stand-in in the CPU test)."""

@@ -2754,3 +2754,67 @@ def sgm_disparity(im, pattern, ndisp=64, p1=7, p2=60, uniq=5, lr=1, want_debug=F
     lib.call('dis_sgm_disparity', im, pattern, disp, dbg and dbg['d_int'], dbg and dbg['vol'], dbg and dbg['census'], n, h, w, ndisp,
              p1, p2, uniq, lr, workspace)
     return (disp, dbg) if want_debug else disp
+
+
+def flow_level_sizes(h, w, min_size=8):
+    """[(h_0, w_0), (h_1, w_1), ...] of dis_dense_flow's pyramid: a further level while min(h, w) >= 2 min_size at the coarsest; every
+    level halves the one before, rounding up"""
+    sizes = [(int(h), int(w))]
+    while min(sizes[-1]) >= 2 * int(min_size) and len(sizes) < 12:
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    return sizes
+
+
+def dense_flow(frames, alpha=1.0, warps=3, iters=64, min_size=8, workspace=None, want_debug=False, debug_level=0, variant=0):
+    """dis_dense_flow: the flow between every ordered pair of the frames (n, tl, H, W) or (n, tl, 1, H, W) of n tracks ->
+    (n, tl * tl, 2, H, W) fp32, entry i * tl + j the flow from frame i to frame j (channel 0 along x), zeros on the diagonal: the
+    `_flow_stacked` layout of the workers.  Coarse-to-fine Horn-Schunck with warping (include/dis_hip.h, section "dense optical flow";
+    tests/flow_ref.py restates it in numpy): alpha > 0 weighs the smoothness term, `warps` (1 .. 16) linearisations per level of
+    `iters` (1 .. 1024) Jacobi steps each, a pyramid level per halving while min(h, w) >= 2 min_size (min_size >= 4); tl 2 .. 4,
+    H and W 8 .. 8192.  want_debug: also a dict with pyr (list over the levels, finest first, of (n, tl, h_k, w_k)), levels (list of
+    (n, tl (tl - 1), 2, h_k, w_k): the flow when level k is left) and warp ((4, n, tl (tl - 1), h, w): the warped second frame, Ix, Iy, It
+    of the last warp at level debug_level).  variant 1: one launch per Jacobi step instead of 8 steps on an LDS-resident tile - the same
+    values, for scripts/flow_rate.py.  The inputs are data: no autograd.  workspace: an optional uint8 tensor of at least
+    dis_flow_workspace(...) bytes to reuse between calls (and what makes the call capturable without an allocation)."""
+    _chk(frames)
+    if not (frames.dim() == 4 or (frames.dim() == 5 and frames.shape[2] == 1)):
+        raise RuntimeError('dense_flow: frames (n, tl, H, W) or (n, tl, 1, H, W) are expected')
+    n, tl, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[-2]), int(frames.shape[-1])
+    alpha, warps, iters, min_size = float(alpha), int(warps), int(iters), int(min_size)
+    need = lib.fn('dis_flow_workspace')(n, tl, h, w, min_size)
+    if need < 0:
+        raise lib.DisHipError(f'dis_flow_workspace: unsupported extents n={n} tl={tl} h={h} w={w} min_size={min_size}')
+    sizes = flow_level_sizes(h, w, min_size)
+    if not (0 < alpha < float('inf') and 1 <= warps <= 16 and 1 <= iters <= 1024 and variant in (0, 1)
+            and 0 <= int(debug_level) < len(sizes)):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'dense_flow: unsupported configuration alpha={alpha} warps={warps} iters={iters} variant={variant} '
+                              f'debug_level={debug_level}')
+    dev = frames.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError('dense_flow: workspace must be a contiguous uint8 CUDA(HIP) tensor')
+    elif workspace.numel() < need or workspace.data_ptr() % 16:
+        raise lib.DisHipError(f'dense_flow: workspace must hold at least {need} bytes and be 16-byte aligned')
+    flow = torch.empty((n, tl * tl, 2, h, w), dtype=torch.float32, device=dev)
+    D = lib.FlowDebug()
+    D.level, D.variant = int(debug_level), int(variant)
+    bufs = None
+    if want_debug:
+        P = n * tl * (tl - 1)
+        bufs = {'pyr': torch.empty(sum(n * tl * a * b for a, b in sizes), dtype=torch.float32, device=dev),
+                'levels': torch.empty(sum(P * 2 * a * b for a, b in sizes), dtype=torch.float32, device=dev),
+                'warp': torch.empty((4, n, tl * (tl - 1)) + sizes[int(debug_level)], dtype=torch.float32, device=dev)}
+        for k_, t_ in bufs.items():
+            setattr(D, k_, t_.data_ptr())
+    lib.call('dis_dense_flow', frames, flow, _ct.addressof(D), n, tl, h, w, alpha, warps, iters, min_size, workspace)
+    if not want_debug:
+        return flow
+    dbg = {'warp': bufs['warp'], 'pyr': [], 'levels': []}
+    o1 = o2 = 0
+    for a, b in sizes:
+        dbg['pyr'].append(bufs['pyr'][o1:o1 + n * tl * a * b].view(n, tl, a, b))
+        dbg['levels'].append(bufs['levels'][o2:o2 + P * 2 * a * b].view(n, tl * (tl - 1), 2, a, b))
+        o1 += n * tl * a * b
+        o2 += P * 2 * a * b
+    return flow, dbg

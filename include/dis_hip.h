@@ -837,6 +837,47 @@ long dis_sgm_workspace(int n, int h, int w, int ndisp);
 int dis_sgm_disparity(const float* im, const float* pattern, float* disp, int* d_int, short* vol, long long* census, int n, int h, int w,
                       int ndisp, int p1, int p2, int uniq, int lr, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- dense optical flow -------- */
+
+/* flow_ij for every ordered pair of frames of a track (csrc/flow.hip): what the multi-frame stage reads from flow.npz, for tracks that
+ * arrive without one.  A coarse-to-fine Horn-Schunck flow with warping, fp32; tests/flow_ref.py restates it in numpy, operand order
+ * included.  Every border is replicate.  x is the column and channel 0, y the row and channel 1; flow_ij(p) is where pixel p of frame i
+ * lies in frame j, minus p (the convention of synth.make_batch).
+ *   normalise  per frame (I - mean) / max(std, 1e-6): its own population mean and standard deviation, accumulated in fp64 in a fixed
+ *              order and rounded once to fp32.  A constant frame becomes zeros.
+ *   pyramid    level 0 is the normalised frame; level k + 1 is level k under [1 4 6 4 1] / 16 over x, then over y - ((p[-2] + p[2]) +
+ *              4 (p[-1] + p[1]) + 6 p[0]) / 16 - at the even rows and columns: ceil(h / 2) x ceil(w / 2).  A further level is built while
+ *              min(h, w) >= 2 min_size at the coarsest.  One pyramid per frame, shared by its pairs.
+ *   bilinear   img at (x, y), both clamped into the image: x0 = floor(x), x1 = min(x0 + 1, w - 1), fx = x - x0 (y alike),
+ *              (I00 (1 - fx) + I01 fx) (1 - fy) + (I10 (1 - fx) + I11 fx) fy.
+ *   per pair   (a, b) = frames (i, j), from the coarsest level to level 0, the flow starting at zero.  On entering a finer level
+ *              u(x, y) = 2 bilinear(u_coarse, x / 2, y / 2), v alike.  Then `warps` times:
+ *                bw = bilinear(b, x + u, y + v); m = (a + bw) / 2; Ix = (m(x + 1) - m(x - 1)) / 2, Iy alike; It = bw - a;
+ *                den = (alpha^2 + Ix^2) + Iy^2; u0 = u, v0 = v; then `iters` Jacobi steps
+ *                ub = ((l + r) + (t + b)) c6 + ((tl + tr) + (bl + br)) c12 over the 8 neighbours of u, c6 = fp32(1 / 6), c12 = fp32(1 / 12),
+ *                vb alike; r = ((Ix (ub - u0) + Iy (vb - v0)) + It) / den; u = ub - Ix r; v = vb - Iy r.
+ * frames (n, tl, h, w), flow (n, tl tl, 2, h, w): DEVICE; entry i tl + j of flow is flow_ij, the diagonal entries are zeros, every
+ * element is written.  dbg: HOST struct, NULL in normal use; every pointer in it may be NULL.  With P = n tl (tl - 1) pairs in the order
+ * track, i, j (j != i):
+ *   pyr      the levels one after another, finest first: level k as (n, tl, h_k, w_k)
+ *   warp     (4, P, h_l, w_l): bw, Ix, Iy, It of the last warp at level l = `level`
+ *   levels   the flow when level k is left, one after another, finest first: level k as (P, 2, h_k, w_k)
+ *   variant  0: the Jacobi steps run 8 per launch on a tile of (u, v) held in LDS; 1: one launch per step from memory - the same
+ *            bits, kept for the rate comparison of scripts/flow_rate.py.
+ * workspace: dis_flow_workspace(n, tl, h, w, min_size) BYTES (-1: unsupported), 16-byte aligned, no initialisation.  No allocation,
+ * no synchronisation, no atomics: capturable, and two calls on the same input give the same bits.
+ * Checks, in this order: NULL frames, flow or workspace -> DIS_ERR_NULL; n <= 0, tl outside 2 .. 4, h or w below 8 or above 8192,
+ * n tl tl 2 h w >= 2^31 -> DIS_ERR_BAD_SHAPE; alpha not positive and finite, warps outside 1 .. 16, iters outside 1 .. 1024,
+ * min_size < 4, a misaligned workspace, a variant other than 0 or 1, warp wanted at a level that does not exist ->
+ * DIS_ERR_UNSUPPORTED.  (The size of the workspace is the caller's to guarantee; ops.dense_flow checks it.) */
+typedef struct DisFlowDebug {
+  float *pyr, *warp, *levels;
+  int level, variant;
+} DisFlowDebug;
+long dis_flow_workspace(int n, int tl, int h, int w, int min_size);
+int dis_dense_flow(const float* frames, float* flow, const DisFlowDebug* dbg, int n, int tl, int h, int w, float alpha, int warps,
+                   int iters, int min_size, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).
