@@ -2818,3 +2818,67 @@ def dense_flow(frames, alpha=1.0, warps=3, iters=64, min_size=8, workspace=None,
         o1 += n * tl * a * b
         o2 += P * 2 * a * b
     return flow, dbg
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# track fusion (csrc/fuse.hip; data/fuse.py writes the point clouds)
+# ----------------------------------------------------------------------------------------------------------------------
+def fuse_track(disp, R, t, K, baseline, value=None, tol=0.01, min_views=2, cap=None, workspace=None, want_dense=False):
+    """dis_fuse_track: the disparity maps disp (n, tl, H, W) or (n, tl, 1, H, W) of n tracks with the poses R (n, tl, 3, 3), t (n, tl, 3)
+    (X_c = R X_w + t), intrinsics K (3 x 3, host: numpy or a CPU tensor) and the baseline -> one point cloud per track in world
+    coordinates (include/dis_hip.h, section "track fusion"; tests/fuse_ref.py restates it in numpy).  A pixel is valid where its
+    disparity is finite and > 0; it is consistent with another frame where its point, projected there, meets that frame's depth within
+    the relative tolerance tol in (0, 1).  A pixel is kept when it is consistent with at least min_views - 1 other frames (1 <= min_views
+    <= tl) and with no earlier one.  value: an optional (n, tl, H, W) or (n, tl, 1, H, W) plane carried along (the ambient image).
+    -> a dict of device tensors: xyz (cap, 3), normal (cap, 3), value (cap) fp32, src (cap) int32 (the linear index of the pixel in
+    disp), count (n) int32.  The records are in ascending src; track b's start at count[:b].sum(); rows at and beyond count.sum() are
+    not written.  cap (default n tl H W: everything fits) bounds the records written, count reports the true numbers.  want_dense: also
+    views, seen, keep (n, tl, H, W) uint8, resid (n, tl, H, W) and point, dnormal (n, tl, 3, H, W) fp32.  The inputs are data: no
+    autograd.  Three launches on the current stream, no synchronisation; workspace: an optional uint8 tensor of at least
+    dis_fuse_workspace(...) bytes to reuse between calls (and what makes the call capturable without an allocation besides the
+    outputs)."""
+    _chk(disp, R, t)
+    if value is not None:
+        _chk(value)
+    if not (disp.dim() == 4 or (disp.dim() == 5 and disp.shape[2] == 1)):
+        raise RuntimeError('fuse_track: disp (n, tl, H, W) or (n, tl, 1, H, W) is expected')
+    n, tl, h, w = int(disp.shape[0]), int(disp.shape[1]), int(disp.shape[-2]), int(disp.shape[-1])
+    if tuple(R.shape) != (n, tl, 3, 3) or tuple(t.shape) != (n, tl, 3):
+        raise RuntimeError('fuse_track: R (n, tl, 3, 3) and t (n, tl, 3) are expected')
+    if value is not None and (value.numel() != disp.numel() or tuple(value.shape[:2]) != (n, tl) or tuple(value.shape[-2:]) != (h, w)):
+        raise RuntimeError('fuse_track: value must have the shape of disp')
+    need = lib.fn('dis_fuse_workspace')(n, tl, h, w)
+    if need < 0:
+        raise lib.DisHipError(f'dis_fuse_workspace: unsupported extents n={n} tl={tl} h={h} w={w}')
+    tol, min_views, baseline = float(tol), int(min_views), float(baseline)
+    K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
+    total = n * tl * h * w
+    cap = total if cap is None else int(cap)
+    fin = lambda v: v == v and abs(v) < float('inf')
+    if not (0.0 < tol < 1.0 and 1 <= min_views <= tl and cap >= 0 and all(fin(v) for v in K4) and K4[0] > 0 and K4[1] > 0
+            and fin(baseline) and baseline > 0):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'fuse_track: unsupported configuration tol={tol} min_views={min_views} cap={cap} K={K4} baseline={baseline}')
+    dev = disp.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError('fuse_track: workspace must be a contiguous uint8 CUDA(HIP) tensor')
+    elif workspace.numel() < need or workspace.data_ptr() % 16:
+        raise lib.DisHipError(f'fuse_track: workspace must hold at least {need} bytes and be 16-byte aligned')
+    res = {'xyz': torch.empty((cap, 3), dtype=torch.float32, device=dev), 'normal': torch.empty((cap, 3), dtype=torch.float32, device=dev),
+           'value': torch.empty((cap,), dtype=torch.float32, device=dev), 'src': torch.empty((cap,), dtype=torch.int32, device=dev),
+           'count': torch.empty((n,), dtype=torch.int32, device=dev)}
+    dense = {k_: torch.empty((n, tl, h, w), dtype=torch.uint8, device=dev) for k_ in ('views', 'seen', 'keep')}
+    dense['resid'] = torch.empty((n, tl, h, w), dtype=torch.float32, device=dev)
+    if want_dense:
+        dense['point'] = torch.empty((n, tl, 3, h, w), dtype=torch.float32, device=dev)
+        dense['dnormal'] = torch.empty((n, tl, 3, h, w), dtype=torch.float32, device=dev)
+    O = lib.FuseOut()
+    for f, _ in lib.FuseOut._fields_:
+        src_ = res if f in res else dense
+        setattr(O, f, (src_[f].data_ptr() or None) if f in src_ else None)
+    lib.call('dis_fuse_track', disp, R, t, lib.host_floats(K4), baseline, value, tol, min_views, cap, _ct.addressof(O), n, tl, h, w,
+             workspace, int(workspace.numel()))
+    if want_dense:
+        res.update(dense)
+    return res

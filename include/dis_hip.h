@@ -878,6 +878,62 @@ long dis_flow_workspace(int n, int tl, int h, int w, int min_size);
 int dis_dense_flow(const float* frames, float* flow, const DisFlowDebug* dbg, int n, int tl, int h, int w, float alpha, int warps,
                    int iters, int min_size, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- track fusion -------------- */
+
+/* The per-frame disparity maps of a track -> one point cloud in world coordinates, with a cross-view consistency measure that needs
+ * no ground truth (csrc/fuse.hip).  Conventions of "track rendering": X_c = R X_w + t, the ray of pixel (u, v) is
+ * ((u - cx) / fx, (v - cy) / fy, 1), disp = fx baseline / z.  fp32; tests/fuse_ref.py restates it in numpy, operand order included.
+ * For track b, frame i, pixel (u, v):
+ *   valid       disp is finite and > 0 (zero, negative, NaN and inf are holes).  z = (fx baseline) / disp, P = (z rx, z ry, z) with
+ *               rx = (u - cx) / fx, ry = (v - cy) / fy; q = P - t_i; X_w = R_i^T q, each component (R[0][k] q0 + R[1][k] q1) + R[2][k] q2.
+ *   projection  into frame j != i: X_j[k] = ((R_j[k][0] X_w0 + R_j[k][1] X_w1) + R_j[k][2] X_w2) + t_j[k];
+ *               u_j = (fx X_j0) / X_j2 + cx, v_j = (fy X_j1) / X_j2 + cy.
+ *   seen in j   the pixel is valid, X_j2 > 0, 0 <= u_j <= w - 1, 0 <= v_j <= h - 1, and the four pixels of the bilinear cell
+ *               x0 = min(floor(u_j), w - 2), y0 = min(floor(v_j), h - 2) are valid in frame j.
+ *   z_s         frame j's DEPTH (fx baseline) / disp interpolated over the cell, ax = u_j - x0, ay = v_j - y0:
+ *               (z00 (1 - ax) + z01 ax) (1 - ay) + (z10 (1 - ax) + z11 ax) ay.
+ *   rel_ij      |z_s - X_j2| / X_j2.  consistent with j: seen and rel_ij <= tol.
+ *   views       1 + the number of consistent j; 0 for an invalid pixel.  seen: the number of j that see the pixel.
+ *   resid       the mean of rel_ij over the seen j (summed in ascending j), 0 with none.
+ *   point       the mean of X_w and of one sample point per consistent j, R_j^T (X_j (z_s / X_j2) - t_j): the point on camera j's ray
+ *               at the sampled depth.  Summed from X_w in ascending j, divided by views.  Zeros for an invalid pixel.
+ *   normal      c = (P(u + 1, v) - P(u - 1, v)) x (P(u, v + 1) - P(u, v - 1)) in camera i, divided by its length
+ *               sqrt((c0 c0 + c1 c1) + c2 c2), negated when (n0 P0 + n1 P1) + n2 P2 > 0 (it faces the camera), rotated by R_i^T.  The zero
+ *               vector where the pixel or one of the four neighbours is invalid or outside the image, or the length is zero or not
+ *               finite.
+ *   value       the pixel of the optional plane carried along (the ambient image); 0 without one.
+ *   keep        valid, views >= min_views, and no j < i is consistent: the lowest-index frame that sees a surface owns it.  That removes
+ *               the tl-fold duplication by a per-pixel rule with no "already used" marking; it leans on consistency being nearly
+ *               symmetric (if pixel p of frame i is consistent with frame j, the surface's pixel in frame j is almost always consistent
+ *               with frame i; where it is not - at the rim of the tolerance, next to holes and image borders - a surface point can be
+ *               kept twice or not at all).
+ * Packed output: the kept pixels in ascending order of src = ((b tl + i) h + v) w + u; track b's records start at the sum of the counts
+ * before it.  If more pixels are kept than `cap`, the first `cap` are written; `count` still holds the true numbers; nothing is
+ * written past `cap`, and records beyond the sum of the counts are not written at all.
+ * disp (n, tl, h, w), R (n, tl, 3, 3), t (n, tl, 3), value (n, tl, h, w) or NULL: DEVICE.  K4_host = {fx, fy, cx, cy}: HOST.
+ * out: HOST struct of DEVICE pointers.  xyz (cap, 3), normal (cap, 3), value (cap) fp32, src (cap) int32 - these four may be NULL
+ * when cap == 0; count (n) int32; the dense maps views, seen, keep (n, tl, h, w) uint8 and resid (n, tl, h, w) fp32 - all written in
+ * full; point, dnormal (n, tl, 3, h, w) fp32 planar, NULL: kept in the workspace.
+ * Three launches: the check kernel (one lane per pixel; the kept count of every 256-pixel block by 64-bit ballots), an exclusive scan of
+ * the block counts by one workgroup (which also forms `count`), the scatter (block offset + rank inside the block).  The hand-off
+ * between them is the launch boundary alone: no atomics, no flags polled between workgroups, so the result does not depend on where
+ * workgroups run and two calls give the same bits.  No allocation, no synchronisation: capturable.
+ * workspace: dis_fuse_workspace(n, tl, h, w) BYTES (-1: unsupported extents), 16-byte aligned, no initialisation.
+ * Checks, in this order, all before any launch: NULL disp, R, t, K4_host, out, workspace, count or a dense map other than point and
+ * dnormal, a NULL packed array with cap > 0 -> DIS_ERR_NULL; n < 1, tl outside 2 .. 4, h or w outside 2 .. 8192, n tl h w >= 2^31 ->
+ * DIS_ERR_BAD_SHAPE; tol not in (0, 1), min_views outside 1 .. tl, fx, fy or baseline not positive and finite, cx or cy not finite,
+ * cap < 0, workspace_bytes below dis_fuse_workspace(...), a misaligned workspace -> DIS_ERR_UNSUPPORTED. */
+typedef struct DisFuseOut {
+  float *xyz, *normal, *value;
+  int *src, *count;
+  unsigned char *views, *seen, *keep;
+  float *resid, *point, *dnormal;
+} DisFuseOut;
+long dis_fuse_workspace(int n, int tl, int h, int w);
+int dis_fuse_track(const float* disp, const float* R, const float* t, const float* K4_host, float baseline, const float* value,
+                   float tol, int min_views, int cap, const DisFuseOut* out, int n, int tl, int h, int w, void* workspace,
+                   long workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).
