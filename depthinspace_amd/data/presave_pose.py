@@ -1,0 +1,255 @@
+"""Pose presave: the camera poses `R` and `t` of frames.npz - which the geometric loss of both workers, FuseNet and data/fuse.py read - for
+tracks that arrive without them.
+
+Rendered and synthetic tracks carry exact poses; a captured track has images only.  Once it has a disparity per frame (sgm_disp from
+data/presave_sgm.py, or a network's from data/presave_disp.py) and a flow per ordered frame pair (data/presave_flow.py), the two are
+dense 3D - 3D correspondences.  For every track directory of a dataset root the chosen disparities and flow.npz go with the K and
+baseline of settings.npz through ops.track_poses - Gauss-Newton per ordered frame pair on the residual in (u, v, disparity), with a
+redescending weight (include/dis_hip.h, section "track poses") - up to four tracks per call.  Frame 0 becomes the world (R_0 = I,
+t_0 = 0); frame j takes the pair (0, j), or the inverse of the pair (j, 0) where that one failed.  R (tl, 3, 3) and t (tl, 3) are added
+to frames.npz through a temporary file; its other arrays stay byte-identical and nothing else is touched.  A track with a frame both of
+whose pairs failed is listed as failed and left as it is.
+
+    python -m depthinspace_amd.data.presave_pose ROOT [--disp gt|sgm|single_frame|multi_frame] [--iters N] [--scale S] [--damping D]
+                                                      [--min-corr N] [--force] [--report] [--pack]
+
+A track that already stores R and t is skipped unless --force is given: rendered tracks keep their exact poses.  --report also
+estimates the tracks that are skipped and prints one line over the dataset: the pairs that are ok / failed, the mean share of the
+pixels a pair uses, its mean weight and weighted rms residual in pixels, and the cycle error - the rotation angle of R_ji R_ij and
+|t_ji + R_ji t_ij| over the median depth of the track, averaged over the unordered pairs: a quality figure that needs no ground truth.
+Where a track stored poses before the run, the rotation angle and the translation error (over the median depth) of the estimated
+relative poses against the stored ones are added.
+
+This is pairwise and nothing more: no bundle adjustment over the track, no loop closure, no estimation of the intrinsics; the pairs
+are independent, and only the pairs with frame 0 set the stored poses.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import packed
+from .dataset import load_settings
+from .fuse import SOURCES
+
+BATCH = 4
+
+
+def load_disp(d, source):
+    """the disparities (tl, H, W) float32 of one track, by the rules of data/fuse.py's load_track: `disp` (gt) or `sgm_disp` (sgm) of
+    frames.npz, or the `disp` of single_frame_disp.npz / multi_frame_disp.npz"""
+    if source not in SOURCES:
+        raise ValueError(f'--disp is one of {SOURCES}')
+    if source in ('gt', 'sgm'):
+        key = 'disp' if source == 'gt' else 'sgm_disp'
+        with np.load(os.path.join(d, 'frames.npz')) as f:
+            if key not in f.files:
+                raise ValueError(f'{d}/frames.npz has no array `{key}`')
+            disp = f[key]
+    else:
+        path = os.path.join(d, f'{source}_disp.npz')
+        if not os.path.exists(path):
+            raise ValueError(f'{path} is missing (data/presave_disp.py writes it)')
+        with np.load(path) as f:
+            disp = f['disp']
+    return np.ascontiguousarray(disp, dtype=np.float32).reshape((disp.shape[0],) + disp.shape[-2:])
+
+
+def load_flow(d, tl):
+    """flow.npz -> (tl tl, 2, H, W) float32 in the layout of ops.dense_flow, zeros on the diagonal"""
+    path = os.path.join(d, 'flow.npz')
+    if not os.path.exists(path):
+        raise ValueError(f'{path} is missing (data/presave_flow.py writes it)')
+    with np.load(path) as f:
+        pairs = {(i, j): np.asarray(f[f'flow_{i}{j}'], dtype=np.float32) for i in range(tl) for j in range(tl) if i != j}
+    h, w = pairs[(0, 1)].shape[-2:]
+    flow = np.zeros((tl * tl, 2, h, w), np.float32)
+    for (i, j), a in pairs.items():
+        flow[i * tl + j] = a.reshape(2, h, w)
+    return flow
+
+
+def stored_poses(d):
+    """(R, t) of frames.npz, or None where it has none"""
+    with np.load(os.path.join(d, 'frames.npz')) as f:
+        if 'R' in f.files and 't' in f.files:
+            return f['R'], f['t']
+    return None
+
+
+def compose_track(R_pair, t_pair, ok):
+    """R_pair (tl, tl, 3, 3), t_pair (tl, tl, 3) (X_j = R_ij X_i + t_ij), ok (tl, tl) bool -> R (tl, 3, 3), t (tl, 3) float32 with frame 0
+    the world: frame j takes the pair (0, j), or the inverse of the pair (j, 0) where that one failed; None if both failed for a frame"""
+    tl = R_pair.shape[0]
+    R, t = np.zeros((tl, 3, 3), np.float64), np.zeros((tl, 3), np.float64)
+    R[0] = np.eye(3)
+    for j in range(1, tl):
+        if ok[0, j]:
+            R[j], t[j] = R_pair[0, j], t_pair[0, j]
+        elif ok[j, 0]:
+            Rj0 = np.asarray(R_pair[j, 0], dtype=np.float64)
+            R[j], t[j] = Rj0.T, -Rj0.T @ np.asarray(t_pair[j, 0], dtype=np.float64)
+        else:
+            return None
+    return R.astype(np.float32), t.astype(np.float32)
+
+
+def relative_poses(R, t):
+    """R (tl, 3, 3), t (tl, 3) -> R_ij = R_j R_i^T (tl, tl, 3, 3), t_ij = t_j - R_ij t_i (tl, tl, 3), float64"""
+    R, t = np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    Rp = np.einsum('jab,icb->ijac', R, R)
+    return Rp, t[None, :, :] - np.einsum('ijab,ib->ija', Rp, t)
+
+
+def rotation_angle(R):
+    """the angle of the rotation(s) R (..., 3, 3) in radians: atan2 of the length of the skew part and (trace - 1) / 2, which stays
+    accurate at small angles where the arc cosine of the trace does not"""
+    R = np.asarray(R, dtype=np.float64)
+    s = 0.5 * np.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], -1)
+    return np.arctan2(np.linalg.norm(s, axis=-1), 0.5 * (np.trace(R, axis1=-2, axis2=-1) - 1.0))
+
+
+def median_depth(disp, fb):
+    """the median of fb / disp over the valid pixels of a track (nan without any)"""
+    d = np.asarray(disp, dtype=np.float64)
+    with np.errstate(invalid='ignore'):
+        ok = np.isfinite(d) & (d > 0)
+    return float(np.median(fb / d[ok])) if ok.any() else float('nan')
+
+
+def report_terms(R_pair, t_pair, stats, pixels, depth, stored=None):
+    """the sums one track adds to the report.  R_pair (tl, tl, 3, 3), t_pair (tl, tl, 3), stats (tl, tl, 4) of ops.track_poses, pixels =
+    H W, depth = the track's median depth, stored = (R, t) or None -> dict: ok, failed (ordered pairs); share, weight, resid (sums over
+    the ok pairs of n / pixels, the mean weight, the rms residual); cycles, cycle_rot, cycle_trans (unordered pairs both of whose
+    directions are ok, and the sums over them); and with stored poses gt_pairs, gt_rot, gt_trans (sums over the ok pairs)"""
+    R_pair, t_pair, stats = (np.asarray(a, dtype=np.float64) for a in (R_pair, t_pair, stats))
+    tl = R_pair.shape[0]
+    off = ~np.eye(tl, dtype=bool)
+    ok = (stats[..., 3] != 0) & off
+    r = {'ok': int(ok.sum()), 'failed': int((off & ~ok).sum()), 'share': float((stats[..., 0][ok] / pixels).sum()),
+         'weight': float(stats[..., 1][ok].sum()), 'resid': float(stats[..., 2][ok].sum()), 'cycles': 0, 'cycle_rot': 0.0, 'cycle_trans': 0.0}
+    for i in range(tl):
+        for j in range(i + 1, tl):
+            if ok[i, j] and ok[j, i]:
+                r['cycles'] += 1
+                r['cycle_rot'] += float(rotation_angle(R_pair[j, i] @ R_pair[i, j]))
+                r['cycle_trans'] += float(np.linalg.norm(t_pair[j, i] + R_pair[j, i] @ t_pair[i, j]) / depth)
+    if stored is not None:
+        Rs, ts = relative_poses(*stored)
+        r['gt_pairs'] = int(ok.sum())
+        r['gt_rot'] = float(rotation_angle(R_pair[ok] @ np.swapaxes(Rs[ok], -1, -2)).sum())
+        r['gt_trans'] = float((np.linalg.norm(t_pair[ok] - ts[ok], axis=-1) / depth).sum())
+    return r
+
+
+def report_line(acc):
+    """the sums of report_terms added over the tracks -> the dict that is printed"""
+    div = lambda a, b: a / b if b else float('nan')
+    res = {'ok': acc['ok'], 'failed': acc['failed'], 'share': div(acc['share'], acc['ok']), 'weight': div(acc['weight'], acc['ok']),
+           'resid': div(acc['resid'], acc['ok']), 'cycle_rot': div(acc['cycle_rot'], acc['cycles']),
+           'cycle_trans': div(acc['cycle_trans'], acc['cycles'])}
+    if acc.get('gt_pairs'):
+        res['gt_rot'] = acc['gt_rot'] / acc['gt_pairs']
+        res['gt_trans'] = acc['gt_trans'] / acc['gt_pairs']
+    return res
+
+
+def _rewrite_with(path, extra):
+    """frames.npz plus (or with other) arrays `extra`: the other arrays are copied as they are; temporary file, then os.replace"""
+    with np.load(path) as f:
+        arrays = {k: f[k] for k in f.files}
+    arrays.update(extra)
+    tmp = path + '.tmp.npz'   # (np.savez appends .npz to any other ending)
+    try:
+        np.savez(tmp, **arrays)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def estimate_pairs(disps, flows, settings, iters=6, scale=1.0, damping=0.0, min_corr=64, device='cuda'):
+    """lists of (tl, H, W) disparities and (tl tl, 2, H, W) flows of tracks of one length, float32 numpy -> R_pair (n, tl, tl, 3, 3),
+    t_pair (n, tl, tl, 3), stats (n, tl, tl, 4) float32 numpy (one call of ops.track_poses)"""
+    from .. import ops
+    dev = torch.device(device)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(np.stack(a), dtype=np.float32)).to(dev)
+    r = ops.track_poses(up(disps), up(flows), np.asarray(settings.K, dtype=np.float32), settings.baseline, iters=iters, scale=scale,
+                        damping=damping, min_corr=min_corr)
+    return tuple(r[k].cpu().numpy() for k in ('R_pair', 't_pair', 'stats'))
+
+
+def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_corr=64, force=False, report=False, pack=False,
+                 device='cuda'):
+    """Adds R (tl, 3, 3) and t (tl, 3) to the frames.npz of every track directory of data_root that has none (force: of all of them),
+    each through a temporary file; the other arrays stay byte-identical.  pack: re-runs packed.pack_dataset.  Returns the number of
+    tracks written, or with report=True - which also estimates the tracks it does not write - the dict of report_line with `tracks`,
+    `written` and `failed_tracks` added (printed as one line).  The tracks that failed are printed by name."""
+    data_root = str(data_root)
+    settings = load_settings(data_root)
+    K = np.asarray(settings.K, dtype=np.float64)
+    fb = float(K[0, 0]) * float(settings.baseline)
+    todo = []
+    for d in packed.track_dirs(data_root):
+        stored = stored_poses(d)
+        write = force or stored is None
+        if write or report:
+            todo.append((d, write, stored))
+    done, failed, acc, k = 0, [], {}, 0
+    while k < len(todo):
+        disps, flows = [], []
+        while k < len(todo) and len(disps) < BATCH:       # up to four tracks of one length per call
+            disp = load_disp(todo[k][0], source)
+            if disps and disp.shape != disps[0].shape:
+                break
+            disps.append(disp)
+            flows.append(load_flow(todo[k][0], disp.shape[0]))
+            k += 1
+        Rp, tp, st = estimate_pairs(disps, flows, settings, iters, scale, damping, min_corr, device)
+        for b, (d, write, stored) in enumerate(todo[k - len(disps):k]):
+            if report:
+                terms = report_terms(Rp[b], tp[b], st[b], disps[b].shape[-2] * disps[b].shape[-1], median_depth(disps[b], fb), stored)
+                for key, v in terms.items():
+                    acc[key] = acc.get(key, 0) + v
+            if not write:
+                continue
+            poses = compose_track(Rp[b], tp[b], st[b][..., 3] != 0)
+            if poses is None:
+                failed.append(d)
+                continue
+            _rewrite_with(os.path.join(d, 'frames.npz'), {'R': poses[0], 't': poses[1]})
+            done += 1
+    if failed:
+        print(f'{len(failed)} tracks failed (a frame without an estimated pair with frame 0) and were left as they are: '
+              + ', '.join(os.path.basename(d) for d in failed))
+    if pack:
+        packed.pack_dataset(data_root)
+    if not report:
+        return done
+    res = report_line(acc) if acc else {}
+    res.update(tracks=len(todo), written=done, failed_tracks=len(failed))
+    print(f'poses from the {source} disparities over {data_root} (iters {iters}, scale {scale:g}, damping {damping:g}): '
+          + '  '.join(f'{key} {v:.6g}' if isinstance(v, float) else f'{key} {v}' for key, v in res.items()))
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m depthinspace_amd.data.presave_pose', description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('root')
+    ap.add_argument('--disp', default='sgm', choices=SOURCES, help='which disparities the poses are estimated from')
+    ap.add_argument('--iters', type=int, default=6, help='Gauss-Newton steps per frame pair (1 .. 64)')
+    ap.add_argument('--scale', type=float, default=1.0, help='scale of the redescending weight, in pixels')
+    ap.add_argument('--damping', type=float, default=0.0, help='this times diag(H) is added to the normal matrix')
+    ap.add_argument('--min-corr', type=int, default=64, help='a pair with fewer usable pixels fails')
+    ap.add_argument('--force', action='store_true', help='also rewrite the poses that are stored')
+    ap.add_argument('--report', action='store_true', help='also print the quality figures over the dataset')
+    ap.add_argument('--pack', action='store_true', help='also (re)write the packed files (data/packed.py)')
+    a = ap.parse_args(argv)
+    r = presave_pose(a.root, a.disp, a.iters, a.scale, a.damping, a.min_corr, force=a.force, report=a.report, pack=a.pack)
+    print(f'{r["written"] if a.report else r} tracks written under {a.root}')
+
+
+if __name__ == '__main__':
+    main()

@@ -2882,3 +2882,50 @@ def fuse_track(disp, R, t, K, baseline, value=None, tol=0.01, min_views=2, cap=N
     if want_dense:
         res.update(dense)
     return res
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# track poses (csrc/pose.hip; data/presave_pose.py writes R and t into frames.npz)
+# ----------------------------------------------------------------------------------------------------------------------
+def track_poses(disp, flow, K, baseline, iters=6, scale=1.0, damping=0.0, min_corr=64, workspace=None):
+    """dis_track_poses: the disparity maps disp (n, tl, H, W) or (n, tl, 1, H, W) of n tracks and the flows between their frames,
+    flow (n, tl * tl, 2, H, W) in the layout of dense_flow (entry i * tl + j the flow from frame i to frame j, the diagonal is not read),
+    with the intrinsics K (3 x 3, host: numpy or a CPU tensor) and the baseline -> the relative pose of every ordered pair of frames
+    (include/dis_hip.h, section "track poses"; tests/pose_ref.py restates it in numpy): X_j = R_pair[b, i, j] X_i + t_pair[b, i, j].
+    `iters` (1 .. 64) Gauss-Newton steps from the identity on the residual in (u, v, disparity) of frame j; after the first step the
+    residuals are weighted by 1 / (1 + r^2 / scale^2)^2 (scale > 0, in pixels); damping >= 0 adds damping * diag(H) to the normal
+    matrix; a pair with fewer than min_corr (>= 6) usable pixels, or a singular system, fails and keeps its last good state.
+    -> a dict of device tensors: R_pair (n, tl, tl, 3, 3), t_pair (n, tl, tl, 3), stats (n, tl, tl, 4) fp32 = {pixels used, mean
+    weight, weighted rms residual in pixels, status (1 ok, 0 failed)}; the diagonal holds the identity.  The inputs are data: no
+    autograd.  2 (iters + 1) launches on the current stream, no synchronisation; workspace: an optional uint8 tensor of at least
+    dis_pose_workspace(...) bytes to reuse between calls (and what makes the call capturable without an allocation besides the
+    outputs)."""
+    _chk(disp, flow)
+    if not (disp.dim() == 4 or (disp.dim() == 5 and disp.shape[2] == 1)):
+        raise RuntimeError('track_poses: disp (n, tl, H, W) or (n, tl, 1, H, W) is expected')
+    n, tl, h, w = int(disp.shape[0]), int(disp.shape[1]), int(disp.shape[-2]), int(disp.shape[-1])
+    if tuple(flow.shape) != (n, tl * tl, 2, h, w):
+        raise RuntimeError('track_poses: flow (n, tl * tl, 2, H, W) is expected')
+    need = lib.fn('dis_pose_workspace')(n, tl, h, w)
+    if need < 0:
+        raise lib.DisHipError(f'dis_pose_workspace: unsupported extents n={n} tl={tl} h={h} w={w}')
+    iters, scale, damping, min_corr, baseline = int(iters), float(scale), float(damping), int(min_corr), float(baseline)
+    K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
+    fin = lambda v: v == v and abs(v) < float('inf')
+    if not (1 <= iters <= 64 and fin(scale) and scale > 0 and fin(damping) and damping >= 0 and min_corr >= 6 and all(fin(v) for v in K4)
+            and K4[0] > 0 and K4[1] > 0 and fin(baseline) and baseline > 0):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'track_poses: unsupported configuration iters={iters} scale={scale} damping={damping} min_corr={min_corr} '
+                              f'K={K4} baseline={baseline}')
+    dev = disp.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError('track_poses: workspace must be a contiguous uint8 CUDA(HIP) tensor')
+    elif workspace.numel() < need or workspace.data_ptr() % 16:
+        raise lib.DisHipError(f'track_poses: workspace must hold at least {need} bytes and be 16-byte aligned')
+    res = {'R_pair': torch.empty((n, tl, tl, 3, 3), dtype=torch.float32, device=dev),
+           't_pair': torch.empty((n, tl, tl, 3), dtype=torch.float32, device=dev),
+           'stats': torch.empty((n, tl, tl, 4), dtype=torch.float32, device=dev)}
+    lib.call('dis_track_poses', disp, flow, lib.host_floats(K4), baseline, iters, scale, damping, min_corr, res['R_pair'], res['t_pair'],
+             res['stats'], n, tl, h, w, workspace, int(workspace.numel()))
+    return res

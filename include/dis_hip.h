@@ -934,6 +934,59 @@ int dis_fuse_track(const float* disp, const float* R, const float* t, const floa
                    float tol, int min_views, int cap, const DisFuseOut* out, int n, int tl, int h, int w, void* workspace,
                    long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- track poses --------------- */
+
+/* The relative camera pose of every ordered pair of frames of a track, from the per-frame disparities and the pairwise flows
+ * (csrc/pose.hip): what gives R and t to a track that arrives with images only.  Conventions of "track rendering" and "track fusion":
+ * X_c = R X_w + t, the ray of pixel (u, v) is ((u - cx) / fx, (v - cy) / fy, 1), disp = fx baseline / z; flow_ij(p) is where pixel p of
+ * frame i lies in frame j, minus p.  For track b and the ordered pair (i, j), i != j, the estimate is the transform from camera-i to
+ * camera-j coordinates, X_j = R_ij X_i + t_ij (R_ij = R_j R_i^T, t_ij = t_j - R_ij t_i): `iters` Gauss-Newton steps, from the identity,
+ * on the residual in (u, v, disparity) of frame j, in pixels.  tests/pose_ref.py restates it in numpy, operand order included.  With
+ * fb = fx baseline (formed in fp32 on the host) and s2 = scale scale (alike), every per-pixel operation below is one fp32 operation:
+ *   valid      disp is finite and > 0.  z = fb / disp, P = (z rx, z ry, z) with rx = (u - cx) / fx, ry = (v - cy) / fy.
+ *   target     in frame j, the same in every pass: uj = u + flow.x, vj = v + flow.y.  The pixel is matched iff it is valid in frame i,
+ *              0 <= uj <= w - 1, 0 <= vj <= h - 1 (comparisons are false for NaN) and the four pixels of the cell x0 = min(floor(uj), w - 2),
+ *              y0 = min(floor(vj), h - 2) are valid in frame j.  ds is frame j's DISPARITY (not the depth: the disparity of a plane is affine
+ *              in the pixel, so the sample is exact there) over the cell, ax = uj - x0, ay = vj - y0:
+ *              ds = (d00 (1 - ax) + d01 ax) (1 - ay) + (d10 (1 - ax) + d11 ax) ay.
+ *              A pixel that is not matched adds nothing (a select, never 0 x).
+ *   state      (R, t) per pair in fp64, set to the identity by the call itself.  Pass k = 0 .. iters uses its fp32 rounding:
+ *              X[c] = ((R[c][0] P0 + R[c][1] P1) + R[c][2] P2) + t[c].  The pixel is used iff it is matched and X2 > 0.
+ *   residual   iz = 1 / X2, px = X0 iz, py = X1 iz; e = ((fx px + cx) - uj, (fy py + cy) - vj, fb iz - ds);
+ *              r2 = (e0 e0 + e1 e1) + e2 e2; g = 1 / (1 + r2 / s2); the weight is 1 in pass 0 and g g afterwards (from the identity every
+ *              residual exceeds `scale`; the first step is the unweighted one).
+ *   Jacobian   of e under a left perturbation X' = X + omega x X + nu.  a = fx iz, b = fy iz, c = fb iz, g0 = -(a px), g1 = -(b py),
+ *              g2 = -(c iz); the rows over (omega, nu), their structural zeros never multiplied:
+ *                J_0 = (g0 X1,         a X2 - g0 X0,   -(a X1),   a, 0, g0)
+ *                J_1 = (g1 X1 - b X2,  -(g1 X0),       b X0,      0, b, g1)
+ *                J_2 = (g2 X1,         -(g2 X0),       0,         0, 0, g2)
+ *   sums       30 per pair and pass: H_pq = sum (weight J_r[p]) J_r[q] for p <= q, g_p = sum (weight J_r[p]) e_r, S_w = sum weight,
+ *              S_c = sum weight r2, n = the number of used pixels.  Every term is formed in fp32, converted to fp64 and added in fp64
+ *              (so the order of the additions changes the result far below one fp32 ulp).
+ *   solve      fp64, one workgroup per pair.  The pair fails if n < min_corr, or if a pivot of the Cholesky factorisation of
+ *              H + damping diag(H) is not > 0 or not finite; a failed pair keeps the state of its last good step (the identity if there
+ *              is none) and takes no further steps.  Else delta = -(H + damping diag(H))^-1 g, omega = delta[0:3], nu = delta[3:6],
+ *              th2 = omega . omega, dR = I + A [omega]x + B [omega]x^2 with A = sin th / th, B = (1 - cos th) / th2 (A = 1, B = 1 / 2 when
+ *              th2 < 1e-16), R <- dR R, t <- dR t + nu.
+ *   closing    after the last step one more pass at the final state, with the weight g g, yields the statistics.
+ * disp (n, tl, h, w), flow (n, tl tl, 2, h, w) - the output layout of dis_dense_flow; the diagonal entries are not read - : DEVICE.
+ * K4_host = {fx, fy, cx, cy}: HOST.  Outputs, DEVICE, every element written: R_pair (n, tl, tl, 3, 3), t_pair (n, tl, tl, 3),
+ * stats (n, tl, tl, 4) = {n, S_w / n, sqrt(S_c / S_w), status} of the closing pass, fp32; status 1: every step was taken, 0: failed; the
+ * ratios are 0 when the pair has no used pixel.  The diagonal is the identity, zeros and {0, 0, 0, 1}.
+ * iters + 1 accumulate launches (each lane a grid-stride range of a pair's pixels - the target is recomputed in every pass, there is no
+ * per-pixel workspace -, a sum over the wave, over the workgroup's waves through LDS, one record of partial sums per workgroup) and
+ * iters + 1 solve launches (the records of a pair added in ascending workgroup order).  The hand-off between them is the launch
+ * boundary alone: no atomics, so two calls give the same bits.  No allocation, no synchronisation: capturable.
+ * workspace: dis_pose_workspace(n, tl, h, w) BYTES (-1: unsupported extents), 16-byte aligned, no initialisation.
+ * Checks, in this order, all before any launch: a NULL pointer -> DIS_ERR_NULL; n < 1, tl outside 2 .. 4, h or w outside 2 .. 8192,
+ * n tl tl 2 h w >= 2^31 -> DIS_ERR_BAD_SHAPE; iters outside 1 .. 64, scale not positive and finite, damping negative or not finite,
+ * min_corr < 6, fx, fy or baseline not positive and finite, cx or cy not finite, workspace_bytes below dis_pose_workspace(...), a
+ * misaligned workspace -> DIS_ERR_UNSUPPORTED. */
+long dis_pose_workspace(int n, int tl, int h, int w);
+int dis_track_poses(const float* disp, const float* flow, const float* K4_host, float baseline, int iters, float scale, float damping,
+                    int min_corr, float* R_pair, float* t_pair, float* stats, int n, int tl, int h, int w, void* workspace,
+                    long workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).
