@@ -171,6 +171,9 @@ SIGS = {
     'dis_fuse_track': 'pppp' + 'f' + 'p' + 'f' + 'ii' + 'p' + 'iiii' + 'pl' + 'p',
     'dis_pose_workspace': 'iiii',
     'dis_track_poses': 'ppp' + 'f' + 'i' + 'ff' + 'i' + 'ppp' + 'iiii' + 'pl' + 'p',
+    'dis_tsdf_integrate': 'pppp' + 'f' + 'pp' + 'ff' + 'ppp' + 'iiiiii' + 'p',
+    'dis_tsdf_mesh_workspace': 'iii',
+    'dis_tsdf_mesh': 'pppp' + 'f' + 'iii' + 'p' + 'iii' + 'pl' + 'p',
     'dis_allreduce_unique_id': 'p',
     'dis_allreduce_init': 'ppii',
     'dis_allreduce_sum_f32': 'pplip',
@@ -179,7 +182,8 @@ SIGS = {
 _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_workspace', 'dis_conv2d_bwd_fused_c16_workspace', 'dis_conv2d_bwd_fused_c16_slots', 'dis_conv2d_bwd_fused_bf16x3_workspace', 'dis_convb_pack_desc_bytes', 'dis_convg_splitk_workspace', 'dis_convb_splitk_workspace', 'dis_conv2d_gnsums_slots', 'dis_conv2d_wgrad_workspace', 'dis_convg_pack_workspace', 'dis_convg_wgrad_workspace',
              'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace', 'dis_geo_loss_bwd_det_workspace',
-             'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace'}
+             'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace',
+             'dis_tsdf_mesh_workspace'}
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}
 _lib = None
@@ -207,6 +211,10 @@ class FlowDebug(ctypes.Structure):   # include/dis_hip.h: DisFlowDebug (device p
 
 class FuseOut(ctypes.Structure):   # include/dis_hip.h: DisFuseOut (device pointers; point and dnormal may be NULL)
     _fields_ = [(n_, ctypes.c_void_p) for n_ in ('xyz', 'normal', 'value', 'src', 'count', 'views', 'seen', 'keep', 'resid', 'point', 'dnormal')]
+
+
+class TsdfMeshOut(ctypes.Structure):   # include/dis_hip.h: DisTsdfMeshOut (device pointers; vid may be NULL)
+    _fields_ = [(n_, ctypes.c_void_p) for n_ in ('xyz', 'normal', 'value', 'views', 'cell', 'faces', 'count', 'vid')]
 
 
 def load():

@@ -2929,3 +2929,107 @@ def track_poses(disp, flow, K, baseline, iters=6, scale=1.0, damping=0.0, min_co
     lib.call('dis_track_poses', disp, flow, lib.host_floats(K4), baseline, iters, scale, damping, min_corr, res['R_pair'], res['t_pair'],
              res['stats'], n, tl, h, w, workspace, int(workspace.numel()))
     return res
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# volumetric fusion (csrc/tsdf.hip; data/mesh.py writes the meshes)
+# ----------------------------------------------------------------------------------------------------------------------
+def _tsdf_fin(v):
+    return v == v and abs(v) < float('inf')
+
+
+def tsdf_integrate(disp, R, t, K, baseline, value=None, *, origin, voxel, trunc, grid):
+    """dis_tsdf_integrate: the disparity maps disp (tl, H, W) or (tl, 1, H, W) of ONE track, 1 <= tl <= 4, with the poses R (tl, 3, 3),
+    t (tl, 3) (X_c = R X_w + t), intrinsics K (3 x 3, host) and the baseline -> a truncated signed distance volume on the lattice
+    origin + (i, j, k) voxel, grid = (nx, ny, nz), each extent in 2 .. 1024 (include/dis_hip.h, section "volumetric fusion";
+    tests/tsdf_ref.py restates it in numpy).  Every lattice point is projected into every frame and reads the nearest pixel; a frame
+    whose depth there lies more than trunc in front of the point is skipped, the others add min(sdf / trunc, 1) with weight 1.
+    value: an optional (tl, H, W) or (tl, 1, H, W) plane carried along (the ambient image), averaged over the frames that see the
+    point within trunc of their surface.  -> tsdf (nz, ny, nx) fp32 (1 where unobserved), weight (nz, ny, nx) uint8, vvalue
+    (nz, ny, nx) fp32.  The inputs are data: no autograd.  One launch on the current stream, no workspace, no synchronisation."""
+    _chk(disp, R, t)
+    if value is not None:
+        _chk(value)
+    if not (disp.dim() == 3 or (disp.dim() == 4 and disp.shape[1] == 1)):
+        raise RuntimeError('tsdf_integrate: disp (tl, H, W) or (tl, 1, H, W) of one track is expected')
+    tl, h, w = int(disp.shape[0]), int(disp.shape[-2]), int(disp.shape[-1])
+    if tuple(R.shape) != (tl, 3, 3) or tuple(t.shape) != (tl, 3):
+        raise RuntimeError('tsdf_integrate: R (tl, 3, 3) and t (tl, 3) are expected')
+    if value is not None and (value.numel() != disp.numel() or int(value.shape[0]) != tl or tuple(value.shape[-2:]) != (h, w)):
+        raise RuntimeError('tsdf_integrate: value must have the shape of disp')
+    nx, ny, nz = (int(g) for g in grid)
+    voxel, trunc, baseline = float(voxel), float(trunc), float(baseline)
+    origin = [float(origin[0]), float(origin[1]), float(origin[2])]
+    K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
+    if not (1 <= tl <= 4 and 2 <= h <= 8192 and 2 <= w <= 8192 and all(2 <= g <= 1024 for g in (nx, ny, nz))):
+        raise lib.DisHipError(f'tsdf_integrate: unsupported extents tl={tl} h={h} w={w} grid={(nx, ny, nz)}')
+    if not (all(_tsdf_fin(v) for v in K4 + origin + [voxel, trunc, baseline]) and voxel > 0 and trunc > 0 and K4[0] > 0 and K4[1] > 0
+            and baseline > 0):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'tsdf_integrate: unsupported configuration voxel={voxel} trunc={trunc} origin={origin} K={K4} '
+                              f'baseline={baseline}')
+    dev = disp.device
+    tsdf = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    weight = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
+    vvalue = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    lib.call('dis_tsdf_integrate', disp, R, t, lib.host_floats(K4), baseline, value, lib.host_floats(origin), voxel, trunc, tsdf, weight,
+             vvalue, tl, h, w, nx, ny, nz)
+    return tsdf, weight, vvalue
+
+
+def tsdf_mesh(tsdf, weight, vvalue, origin, voxel, min_weight=1, vcap=None, fcap=None, workspace=None, want_dense=False):
+    """dis_tsdf_mesh: the volume tsdf (nz, ny, nx) fp32, weight (nz, ny, nx) uint8, vvalue (nz, ny, nx) fp32 of tsdf_integrate -> an
+    indexed triangle mesh by naive surface nets (include/dis_hip.h, section "volumetric fusion"; tests/tsdf_ref.py restates it in
+    numpy): one vertex per cell whose eight corners have weight >= min_weight (1 .. 4) and differ in the sign of tsdf, one quad - two
+    triangles, their normals towards free space - per lattice edge that crosses the surface between four such cells.
+    -> a dict of device tensors: xyz (vcap, 3), normal (vcap, 3), value (vcap) fp32, views (vcap) uint8 (the smallest corner weight),
+    cell (vcap) int32 (ascending linear cell indices), faces (fcap, 3) int32, count (2) int32 = the true numbers of vertices and
+    triangles; want_dense: also vid (nz - 1, ny - 1, nx - 1) int32, the vertex id of every cell or -1.  Rows at or beyond a cap are not
+    written, nor is a triangle that names a vertex >= vcap.  With vcap and fcap given the call is five launches on the current stream
+    with no synchronisation, and capturable when a workspace (uint8, at least dis_tsdf_mesh_workspace(nx, ny, nz) bytes, 16-byte
+    aligned) is given too.  A cap left None is found by a counting call first - which reads `count` back, so it synchronises - and
+    the outputs are then exactly as long as the mesh.  The inputs are data: no autograd."""
+    _chk(tsdf, vvalue)
+    if not (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.is_contiguous()):
+        raise RuntimeError('tsdf_mesh: weight must be a contiguous CUDA(HIP) tensor: the HIP path is the only path')
+    if tsdf.dim() != 3 or tuple(weight.shape) != tuple(tsdf.shape) or tuple(vvalue.shape) != tuple(tsdf.shape):
+        raise RuntimeError('tsdf_mesh: tsdf, weight and vvalue (nz, ny, nx) are expected')
+    if tsdf.dtype != torch.float32 or vvalue.dtype != torch.float32 or weight.dtype != torch.uint8:
+        raise RuntimeError('tsdf_mesh: tsdf and vvalue are float32, weight is uint8')
+    nz, ny, nx = (int(v) for v in tsdf.shape)
+    need = lib.fn('dis_tsdf_mesh_workspace')(nx, ny, nz)
+    if need < 0:
+        raise lib.DisHipError(f'dis_tsdf_mesh_workspace: unsupported extents nx={nx} ny={ny} nz={nz}')
+    voxel, min_weight = float(voxel), int(min_weight)
+    origin = [float(origin[0]), float(origin[1]), float(origin[2])]
+    if not (all(_tsdf_fin(v) for v in origin + [voxel]) and voxel > 0 and 1 <= min_weight <= 4
+            and (vcap is None or int(vcap) >= 0) and (fcap is None or int(fcap) >= 0)):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'tsdf_mesh: unsupported configuration voxel={voxel} origin={origin} min_weight={min_weight} vcap={vcap} '
+                              f'fcap={fcap}')
+    dev = tsdf.device
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError('tsdf_mesh: workspace must be a contiguous uint8 CUDA(HIP) tensor')
+    elif workspace.numel() < need or workspace.data_ptr() % 16:
+        raise lib.DisHipError(f'tsdf_mesh: workspace must hold at least {need} bytes and be 16-byte aligned')
+    origin_h = lib.host_floats(origin)
+
+    def run(vc, fc, dense):
+        res = {'xyz': torch.empty((vc, 3), dtype=torch.float32, device=dev), 'normal': torch.empty((vc, 3), dtype=torch.float32, device=dev),
+               'value': torch.empty((vc,), dtype=torch.float32, device=dev), 'views': torch.empty((vc,), dtype=torch.uint8, device=dev),
+               'cell': torch.empty((vc,), dtype=torch.int32, device=dev), 'faces': torch.empty((fc, 3), dtype=torch.int32, device=dev),
+               'count': torch.empty((2,), dtype=torch.int32, device=dev)}
+        if dense:
+            res['vid'] = torch.empty((nz - 1, ny - 1, nx - 1), dtype=torch.int32, device=dev)
+        O = lib.TsdfMeshOut()
+        for f, _ in lib.TsdfMeshOut._fields_:
+            setattr(O, f, (res[f].data_ptr() or None) if f in res else None)
+        lib.call('dis_tsdf_mesh', tsdf, weight, vvalue, origin_h, voxel, min_weight, vc, fc, _ct.addressof(O), nx, ny, nz, workspace,
+                 int(workspace.numel()))
+        return res
+
+    if vcap is None or fcap is None:
+        nv, nf = (int(v) for v in run(0, 0, False)['count'].tolist())
+        vcap = nv if vcap is None else int(vcap)
+        fcap = nf if fcap is None else int(fcap)
+    return run(int(vcap), int(fcap), want_dense)

@@ -987,6 +987,78 @@ int dis_track_poses(const float* disp, const float* flow, const float* K4_host, 
                     int min_corr, float* R_pair, float* t_pair, float* stats, int n, int tl, int h, int w, void* workspace,
                     long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- volumetric fusion --------- */
+
+/* The per-frame disparity maps of ONE track -> a truncated signed distance volume on a regular lattice, and the volume -> an indexed
+ * triangle mesh by naive surface nets (csrc/tsdf.hip).  Conventions of "track rendering" and "track fusion": X_c = R X_w + t,
+ * disp = fx baseline / z, a disparity is valid when it is finite and > 0.  fp32; tests/tsdf_ref.py restates both in numpy, operand
+ * order included.  One track per call (a volume can fill the device); no atomics: two calls give the same bits.
+ *
+ * dis_tsdf_integrate.  fb = fx baseline is formed in fp32 on the host.  For lattice point (i, j, k), 0 <= i < nx and so on,
+ *   X = (ox + float(i) voxel, oy + float(j) voxel, oz + float(k) voxel), formed from the indices for every point on its own.
+ * For the frames f = 0 .. tl - 1, in this order:
+ *   Xc_r = ((R_f[r][0] X0 + R_f[r][1] X1) + R_f[r][2] X2) + t_f[r]; z = Xc_2.  The frame is skipped unless z > 0.
+ *   pu = floor((fx (Xc_0 / z) + cx) + 0.5), pv = floor((fy (Xc_1 / z) + cy) + 0.5): the NEAREST pixel (a bilinear depth across a
+ *   silhouette would invent surface).  The frame is skipped unless 0 <= pu <= w - 1 and 0 <= pv <= h - 1, compared as floats before
+ *   any conversion to an integer (false for NaN).
+ *   d = disp[f][pv][pu]; skipped unless valid.  depth = fb / d, sdf = depth - z.  Skipped if sdf < -trunc (behind the surface).
+ *   Otherwise acc = acc + min(sdf / trunc, 1), weight = weight + 1, and where sdf <= trunc also vsum = vsum + value[f][pv][pu],
+ *   vcnt = vcnt + 1.
+ * tsdf = acc / float(weight), or 1 where weight is 0; vvalue = vsum / float(vcnt), or 0 where vcnt is 0 (and everywhere without a
+ * value plane).  Every frame weighs 1.
+ * disp (tl, h, w), R (tl, 3, 3), t (tl, 3), value (tl, h, w) or NULL: DEVICE.  K4_host = {fx, fy, cx, cy}, origin3_host = {ox, oy, oz}:
+ * HOST.  Outputs, DEVICE, every element written: tsdf (nz, ny, nx) fp32, weight (nz, ny, nx) uint8, vvalue (nz, ny, nx) fp32.
+ * One launch, one lane per lattice point, the lanes along x; no workspace, no allocation, no synchronisation: capturable.
+ * Checks, in this order, all before the launch: a NULL pointer other than value -> DIS_ERR_NULL; tl outside 1 .. 4, h or w outside
+ * 2 .. 8192, nx, ny or nz outside 2 .. 1024 -> DIS_ERR_BAD_SHAPE; voxel, trunc, fx, fy, baseline or fx baseline not positive and
+ * finite, cx, cy or a component of the origin not finite -> DIS_ERR_UNSUPPORTED. */
+int dis_tsdf_integrate(const float* disp, const float* R, const float* t, const float* K4_host, float baseline, const float* value,
+                       const float* origin3_host, float voxel, float trunc, float* tsdf, unsigned char* weight, float* vvalue, int tl,
+                       int h, int w, int nx, int ny, int nz, void* stream);
+
+/* dis_tsdf_mesh: naive surface nets (one vertex per cell the surface passes through, one quad per lattice edge it crosses: no case
+ * table, shared vertices by construction).  neg(p) = tsdf[p] < 0.
+ *   cell      (i, j, k), i <= nx - 2 and so on, has the corners c = 0 .. 7 at the offsets (c & 1, c >> 1 & 1, c >> 2).  It is active when
+ *             all eight corner weights are >= min_weight and the eight neg bits are neither all set nor all clear.
+ *   edges     the 12 cell edges in the order: axis a = x, y, z; inside an axis (p, q) = (0, 0), (0, 1), (1, 0), (1, 1), p the offset
+ *             along axis a + 1 and q along a + 2 (cyclic).  lo is the corner with offset 0 along a, hi the one with offset 1;
+ *             fa = tsdf[lo], fb = tsdf[hi].  An edge with neg(lo) != neg(hi) adds the point with fa / (fa - fb) along a, float(p) and
+ *             float(q) along the others, to three running sums (sum = sum + coordinate, from 0, in edge order) and 1 to their number.
+ *   vertex    local = sum / float(number); position o + (float(index) + local) voxel per axis.  normal: g_a = the sum of (fb - fa) over
+ *             the four edges of axis a (from the first difference, in edge order), divided by sqrt((g0 g0 + g1 g1) + g2 g2) - towards
+ *             positive tsdf, which is free space -, zeros when that length is zero or not finite.  value: the eight corner vvalues
+ *             added in corner order, from corner 0, divided by 8.  views: the smallest corner weight.
+ *   ids       vertex ids are the ranks of the active cells in the linear order (k, j, i); cell = (k (ny - 1) + j) (nx - 1) + i.
+ *   faces     every lattice point p and axis a (x, y, z) with p_a <= n_a - 2 and 1 <= p_b <= n_b - 2 on the two other axes yields a quad
+ *             when neg(p) != neg(p + e_a) and the four cells at the offsets (-1, -1), (0, -1), (0, 0), (-1, 0) along (a + 1, a + 2) - and
+ *             p_a along a - are all active.  Their vertex ids in this order are (q0, q1, q2, q3); the order is reversed when tsdf[p] >= 0
+ *             (not neg(p)).  Two triangles (q0, q1, q2), (q0, q2, q3), so that the face normals point to free space.  Faces are ordered
+ *             by the linear index of p, then by axis.
+ * tsdf, weight, vvalue (nz, ny, nx): DEVICE.  origin3_host: HOST.  out: HOST struct of DEVICE pointers.  xyz (vcap, 3), normal (vcap, 3),
+ * value (vcap) fp32, views (vcap) uint8, cell (vcap) int32 ascending - these five may be NULL when vcap == 0; faces (fcap, 3) int32, may be
+ * NULL when fcap == 0; count (2) int32 = the true numbers of vertices and of triangles, whatever the caps (int32: more than 2^31 - 1
+ * triangles are not counted right); vid (nz - 1, ny - 1, nx - 1) int32, the dense vertex ids, -1 where the cell is inactive, NULL: kept in
+ * the workspace.  Rows at or beyond a cap are not written, nor is a triangle that names a vertex >= vcap (it is still counted); rows at
+ * and beyond the counts are not written at all.
+ * Five launches: flags (the eight-corner stencil of a 256-point block staged in LDS as four linear rows of 257; the active count of
+ * every block by 64-bit ballots), quads (the quad count of every block), one scan of both count arrays (a workgroup each, which also
+ * forms `count`), vertices (block offset + rank inside the block), faces.  The hand-off between them is the launch boundary alone: no
+ * atomics, no flags polled between workgroups.  No allocation, no synchronisation: capturable.
+ * workspace: dis_tsdf_mesh_workspace(nx, ny, nz) BYTES (-1: unsupported extents), 16-byte aligned, no initialisation.
+ * Checks, in this order, all before any launch: NULL tsdf, weight, vvalue, origin3_host, out, workspace or count, a NULL vertex array
+ * with vcap > 0, NULL faces with fcap > 0 -> DIS_ERR_NULL; nx, ny or nz outside 2 .. 1024 -> DIS_ERR_BAD_SHAPE; voxel not positive and
+ * finite, a component of the origin not finite, min_weight outside 1 .. 4 (the longest track), vcap or fcap < 0, workspace_bytes below
+ * dis_tsdf_mesh_workspace(...), a misaligned workspace -> DIS_ERR_UNSUPPORTED. */
+typedef struct DisTsdfMeshOut {
+  float *xyz, *normal, *value;
+  unsigned char* views;
+  int *cell, *faces, *count, *vid;
+} DisTsdfMeshOut;
+long dis_tsdf_mesh_workspace(int nx, int ny, int nz);
+int dis_tsdf_mesh(const float* tsdf, const unsigned char* weight, const float* vvalue, const float* origin3_host, float voxel,
+                  int min_weight, int vcap, int fcap, const DisTsdfMeshOut* out, int nx, int ny, int nz, void* workspace,
+                  long workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).
