@@ -65,7 +65,8 @@ extern "C" int dis_act_bwd_ld(const float* gy, int ldg, const float* y, int ldy,
 }
 
 // dis_act_bwd_ld that also leaves the bias gradient (column sums of gpre) behind: one pass over the gradient tensor instead of two.
-// c / 4 divides 256: a thread keeps its 4 channels while it walks down the pixels; per-block fp32 partials, fp64 totals.
+// c / 4 divides 256: a thread keeps its 4 channels while it walks down the pixels; its fp32 sums are added over the block's rows in
+// fp64, stored as per-block fp32 partials, and totalled in fp64.
 #define ABB_BLOCKS 1024
 __global__ __launch_bounds__(256) void act_bwd_ld_bias_kernel(const float* __restrict__ gy, int ldg, const float* __restrict__ y,
                                                                int ldy, float4* __restrict__ gp, int act, long npix, int c4,
@@ -88,9 +89,9 @@ __global__ __launch_bounds__(256) void act_bwd_ld_bias_kernel(const float* __res
   __syncthreads();
   const int c = c4 * 4;
   for (int t = threadIdx.x; t < c; t += 256) {
-    float acc = 0.f;
-    for (int r = 0; r < rows; ++r) acc += red[(r * c4 + (t >> 2)) * 4 + (t & 3)];
-    part[(long)blockIdx.x * c + t] = acc;
+    double acc = 0.0;  // (up to 256 rows: an fp32 chain here would carry 256 roundings of the block's partial)
+    for (int r = 0; r < rows; ++r) acc += (double)red[(r * c4 + (t >> 2)) * 4 + (t & 3)];
+    part[(long)blockIdx.x * c + t] = (float)acc;
   }
 }
 __global__ __launch_bounds__(256) void act_bias_final_kernel(const float* __restrict__ part, int nblocks, int c,

@@ -7,11 +7,38 @@ The reference uses torch.optim.Adam(lr=1e-4) on a single GPU (train_val.py:55-56
 parallelism here is batch sharding with mean-of-per-rank gradients: rank r owns its own tracks,
 every rank holds full replicas of the parameters and of the Adam state.
 """
+import contextlib
+import gc
 import os
 
 import torch
 
 from . import ops
+
+
+@contextlib.contextmanager
+def no_gc():
+    """Collect now, then keep Python's cyclic collector off for the block.  For stream captures: torch.cuda.graph no longer collects
+    on entry (torch >= 2.9), and a torch.cuda.CUDAGraph that a dead reference cycle still holds may be destroyed by a collection
+    that happens to start INSIDE another capture.  On ROCm its destructor synchronises the device, which a capture in progress
+    forbids; the error is thrown from a destructor and the process aborts.  Whether it happens depends only on how many
+    objects the process allocated before (the collector's counters): an unrelated change moves it."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was:
+            gc.enable()
+
+
+@contextlib.contextmanager
+def graph_capture(graph, **kwargs):
+    """torch.cuda.graph(graph, **kwargs) with no finaliser running inside the capture (no_gc)"""
+    with no_gc():
+        with torch.cuda.graph(graph, **kwargs):
+            yield
 
 
 def init_distributed(backend=None):
@@ -499,7 +526,7 @@ class GraphedStep(object):
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g1):
+        with graph_capture(g1):
             self._forward_loss().backward()
             opt.step(all_reduce=False)
         self._graphs, self.mode = (g1,), 'graph'

@@ -8,6 +8,8 @@ import functools
 import pytest
 import torch
 
+from depthinspace_amd.trainer import graph_capture   # (torch.cuda.graph with the cyclic collector held off: see its docstring)
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(8, 4, 3, 3), (8,), (33,)]
@@ -82,7 +84,7 @@ class _Stepper(object):
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        with graph_capture(self.graph):
             opt.flat_g.copy_(self.gin)
             opt.step(all_reduce=False)
 
@@ -302,7 +304,7 @@ def test_norm_and_clipped_step_repeat_bit_for_bit(which):
     t = fresh()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with graph_capture(graph):
         call(t)
     graph.replay()
     graph.replay()

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from depthinspace_amd.trainer import graph_capture   # (torch.cuda.graph with the cyclic collector held off: see its docstring)
+
 from tests import flow_ref
 
 pytestmark = pytest.mark.gpu
@@ -151,7 +153,7 @@ def test_graph_capture_on_a_side_stream(shape):
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
+    with graph_capture(graph, stream=side):
         out = ops.dense_flow(fr_d, workspace=ws, **PARAMS[0])
     fr_d.copy_(torch.from_numpy(fr))                 # the capture executed nothing: the replay sees the frames
     graph.replay()

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from depthinspace_amd.trainer import graph_capture   # (torch.cuda.graph with the cyclic collector held off: see its docstring)
+
 from tests import fuse_inputs as FI
 from tests import fuse_ref
 
@@ -180,7 +182,7 @@ def test_graph_capture_on_a_side_stream(shape):
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
+    with graph_capture(graph, stream=side):
         out = ops.fuse_track(disp_d, R, t, a['K'], a['baseline'], val, workspace=ws, want_dense=True)
     disp_d.copy_(_dev(a['disp']))                    # the capture executed nothing: the replay sees the disparities
     graph.replay()

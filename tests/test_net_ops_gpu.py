@@ -4,6 +4,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+from depthinspace_amd.trainer import graph_capture   # (torch.cuda.graph with the cyclic collector held off: see its docstring)
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
@@ -985,7 +987,7 @@ def test_adam_graph_replay_matches_torch():
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
     load(1)
-    with torch.cuda.graph(graph):
+    with graph_capture(graph):
         opt.flat_g.copy_(gin)
         opt.step(all_reduce=False)
     for k in range(2, 5):   # the capture itself executed nothing: replays are steps 2, 3, 4 (k = 1 .. 3 of the data)

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from depthinspace_amd.trainer import graph_capture   # (torch.cuda.graph with the cyclic collector held off: see its docstring)
+
 from tests import pose_inputs as PI
 from tests import pose_ref
 
@@ -128,7 +130,7 @@ def test_graph_capture_on_a_side_stream(shape):
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
+    with graph_capture(graph, stream=side):
         out = ops.track_poses(disp_d, flow_d, a['K'], a['baseline'], min_corr=PI.MIN_CORR, workspace=ws)
     disp_d.copy_(_dev(a['disp']))                    # the capture executed nothing: the replay sees the inputs
     flow_d.copy_(_dev(a['flow']))

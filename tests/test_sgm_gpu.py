@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from depthinspace_amd.trainer import graph_capture   # (torch.cuda.graph with the cyclic collector held off: see its docstring)
+
 from tests import sgm_ref
 
 pytestmark = pytest.mark.gpu
@@ -102,7 +104,7 @@ def test_graph_capture_on_a_side_stream(shape):
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
+    with graph_capture(graph, stream=side):
         out = ops.sgm_disparity(im_d, pat_d, ndisp=D, workspace=ws)
     im_d.copy_(torch.from_numpy(im))                # the capture executed nothing: the replay sees the frames
     graph.replay()

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from depthinspace_amd.trainer import graph_capture   # (torch.cuda.graph with the cyclic collector held off: see its docstring)
+
 from tests import tsdf_inputs as TI
 from tests import tsdf_ref
 
@@ -245,7 +247,7 @@ def test_graph_capture_on_a_side_stream(case):
     side = torch.cuda.Stream()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
+    with graph_capture(graph, stream=side):
         gvol = ops.tsdf_integrate(disp_d, R, t, a['K'], a['baseline'], val, origin=origin, voxel=voxel, trunc=trunc, grid=grid)
         out = ops.tsdf_mesh(gvol[0], gvol[1], gvol[2], origin, voxel, vcap=nv + 5, fcap=nf + 5, workspace=ws, want_dense=True)
     disp_d.copy_(_dev(a['disp']))                    # the capture executed nothing: the replay sees the disparities
