@@ -15,7 +15,7 @@
 //                          the image's, that side stays exact.  Rows that can no longer reach the interior are skipped.
 //   flow_jacobi_step_kernel  one step per launch from global memory: the variant scripts/flow_rate.py measures the above against.
 //   flow_store_kernel      (pairs, 2, h, w) -> flow (n, tl tl, 2, h, w) with the zero diagonal.
-#include "common.h"
+#include "track_common.h"
 
 #define FLOW_T 8
 #define FLOW_RW 64
@@ -323,12 +323,13 @@ struct FlowPlan {
   long stats, pyr, uv[3], coef, total;   // float offsets inside the workspace
 };
 
-static inline long flow_align4(long v) { return (v + 3) & ~3L; }
+static bool flow_extents_ok(int n, int tl, int h, int w) {
+  return n > 0 && tl >= 2 && tl <= TRACK_MAX_TL && track_image_ok(h, w, 8) && (long)n * tl * tl * 2 * h * w <= 0x7fffffffL;
+}
 
 // false: unsupported extents
 static bool flow_plan(int n, int tl, int h, int w, int min_size, FlowPlan* pl) {
-  if (n <= 0 || tl < 2 || tl > 4 || h < 8 || w < 8 || h > 8192 || w > 8192 || min_size < 4) return false;
-  if ((long)n * tl * tl * 2 * h * w > 0x7fffffffL) return false;
+  if (!flow_extents_ok(n, tl, h, w) || min_size < 4) return false;
   pl->frames = (long)n * tl;
   pl->pairs = (long)n * tl * (tl - 1);
   int k = 0;
@@ -346,18 +347,12 @@ static bool flow_plan(int n, int tl, int h, int w, int min_size, FlowPlan* pl) {
   }
   pl->levels = k + 1;
   const long hw = (long)h * w;
-  long o = 0;
-  pl->stats = o;
-  o = flow_align4(o + 2 * pl->frames);
-  pl->pyr = o;
-  o = flow_align4(o + pl->pyr_off[pl->levels]);
-  for (int b = 0; b < 3; ++b) {
-    pl->uv[b] = o;
-    o = flow_align4(o + pl->pairs * 2 * hw);
-  }
-  pl->coef = o;
-  o = flow_align4(o + pl->pairs * 3 * hw);
-  pl->total = o;
+  TrackCarver ws = {4, 0};   // in floats: 16 bytes
+  pl->stats = ws.take(2 * pl->frames);
+  pl->pyr = ws.take(pl->pyr_off[pl->levels]);
+  for (int b = 0; b < 3; ++b) pl->uv[b] = ws.take(pl->pairs * 2 * hw);
+  pl->coef = ws.take(pl->pairs * 3 * hw);
+  pl->total = ws.off;
   return true;
 }
 
@@ -370,8 +365,7 @@ extern "C" long dis_flow_workspace(int n, int tl, int h, int w, int min_size) {
 extern "C" int dis_dense_flow(const float* frames, float* flow, const DisFlowDebug* dbg, int n, int tl, int h, int w, float alpha, int warps,
                               int iters, int min_size, void* workspace, void* stream) {
   if (!frames || !flow || !workspace) return DIS_ERR_NULL;
-  if (n <= 0 || tl < 2 || tl > 4 || h < 8 || w < 8 || h > 8192 || w > 8192 || (long)n * tl * tl * 2 * h * w > 0x7fffffffL)
-    return DIS_ERR_BAD_SHAPE;
+  if (!flow_extents_ok(n, tl, h, w)) return DIS_ERR_BAD_SHAPE;
   FlowPlan pl;
   if (!(alpha > 0.f) || !(alpha <= 3.0e38f) || warps < 1 || warps > 16 || iters < 1 || iters > 1024 || min_size < 4 ||
       ((uintptr_t)workspace & 15) || !flow_plan(n, tl, h, w, min_size, &pl))

@@ -13,33 +13,17 @@
 //                        the per-track counts (a track's tl ceil(h w / 256) blocks are contiguous).
 //   fuse_scatter_kernel  the same grid as the check: a kept pixel writes its record at block offset + rank inside the block (ballot of
 //                        `keep`, popcount of the lower lanes, the waves before it through LDS); records at or beyond `cap` are dropped.
-#include "common.h"
+#include "track_common.h"
 
-#define FUSE_BLOCK 256
-#define FUSE_SCAN 1024
-#define FUSE_MAX_TL 4
+#define FUSE_BLOCK TRACK_BLOCK
+#define FUSE_MAX_TL TRACK_MAX_TL
 
 struct FuseParams {
   int n, tl, h, w, hw, bpf;              // bpf = blocks per frame
-  float fx, fy, cx, cy, fb, tol;         // fb = fx * baseline
+  TrackCamera cam;
+  float tol;
   int min_views, cap;
 };
-
-__device__ __forceinline__ bool fuse_valid(float d) { return d > 0.f && d <= 3.4028234663852886e38f; }   // finite and > 0 (NaN: false)
-
-__device__ __forceinline__ void fuse_backproject(float d, int u, int v, const FuseParams& p, float* P) {
-  const float z = p.fb / d;
-  P[0] = z * (((float)u - p.cx) / p.fx);
-  P[1] = z * (((float)v - p.cy) / p.fy);
-  P[2] = z;
-}
-
-// R^T (a - t), each component (R[0][k] q0 + R[1][k] q1) + R[2][k] q2
-__device__ __forceinline__ void fuse_to_world(const float* __restrict__ R, const float* __restrict__ t, const float* a, float* X) {
-  const float q0 = a[0] - t[0], q1 = a[1] - t[1], q2 = a[2] - t[2];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) X[k] = (R[k] * q0 + R[3 + k] * q1) + R[6 + k] * q2;
-}
 
 __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __restrict__ disp, const float* __restrict__ R,
                                                                 const float* __restrict__ t, unsigned char* __restrict__ views_o,
@@ -47,7 +31,6 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __r
                                                                 float* __restrict__ resid_o, float* __restrict__ point_o,
                                                                 float* __restrict__ normal_o, int* __restrict__ block_count,
                                                                 const FuseParams p) {
-  __shared__ int wave_count[FUSE_BLOCK / DIS_WAVE];
   const int frame = blockIdx.x / p.bpf;                                // b tl + i: uniform over the block
   const int pix = (blockIdx.x % p.bpf) * FUSE_BLOCK + threadIdx.x;     // inside the frame: (v, u)
   const int i = frame % p.tl;
@@ -63,15 +46,15 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __r
     const bool interior = u > 0 && u < p.w - 1 && v > 0 && v < p.h - 1;
     const float dl = di[interior ? pix - 1 : pix], dr = di[interior ? pix + 1 : pix];
     const float du = di[interior ? pix - p.w : pix], dd = di[interior ? pix + p.w : pix];
-    const bool valid = fuse_valid(d);
+    const bool valid = track_valid(d);
     int views = 0, seen = 0;
     float resid = 0.f, pt[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f};
     if (valid) {
       const float* Ri = R + frame * 9;
       const float* ti = t + frame * 3;
       float P[3], Xw[3];
-      fuse_backproject(d, u, v, p, P);
-      fuse_to_world(Ri, ti, P, Xw);
+      track_backproject(d, u, v, p.cam, P);
+      track_to_world(Ri, ti, P, Xw);
       // first every projection and its four taps (slot s is frame j = s + (s >= i): ascending j), then the arithmetic
       float Xj[FUSE_MAX_TL - 1][3], uj[FUSE_MAX_TL - 1], vj[FUSE_MAX_TL - 1], tap[FUSE_MAX_TL - 1][4];
       int x0[FUSE_MAX_TL - 1], y0[FUSE_MAX_TL - 1];
@@ -81,12 +64,13 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __r
         ok[s] = false;
         if (s < p.tl - 1) {
           const int j = s + (s >= i ? 1 : 0);
-          const float* Rj = R + (frame0 + j) * 9;
-          const float* tj = t + (frame0 + j) * 3;
+          float Y[3];   // (handing the helper the row Xj[s] itself costs four registers and reorders the blocks)
+          track_to_camera(R + (frame0 + j) * 9, t + (frame0 + j) * 3, Xw, Y);
 #pragma unroll
-          for (int k = 0; k < 3; ++k) Xj[s][k] = ((Rj[3 * k] * Xw[0] + Rj[3 * k + 1] * Xw[1]) + Rj[3 * k + 2] * Xw[2]) + tj[k];
-          uj[s] = (p.fx * Xj[s][0]) / Xj[s][2] + p.cx;
-          vj[s] = (p.fy * Xj[s][1]) / Xj[s][2] + p.cy;
+          for (int k = 0; k < 3; ++k) Xj[s][k] = Y[k];
+          // this projection is fuse's own: pose has fx * (X0 * (1 / X2)) + cx, tsdf fx * (x / zs) + cx, rounded
+          uj[s] = (p.cam.fx * Xj[s][0]) / Xj[s][2] + p.cam.cx;
+          vj[s] = (p.cam.fy * Xj[s][1]) / Xj[s][2] + p.cam.cy;
           // (every comparison is false for NaN)
           ok[s] = Xj[s][2] > 0.f && uj[s] >= 0.f && uj[s] <= (float)(p.w - 1) && vj[s] >= 0.f && vj[s] <= (float)(p.h - 1);
           // 0 <= x0 <= w - 2, 0 <= y0 <= h - 2; a pixel that frame j does not see reads the cell at the origin and drops it
@@ -105,10 +89,10 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __r
         if (!ok[s]) continue;
         const int j = s + (s >= i ? 1 : 0);
         const float d00 = tap[s][0], d01 = tap[s][1], d10 = tap[s][2], d11 = tap[s][3];
-        if (!(fuse_valid(d00) && fuse_valid(d01) && fuse_valid(d10) && fuse_valid(d11))) continue;
+        if (!(track_valid(d00) && track_valid(d01) && track_valid(d10) && track_valid(d11))) continue;
         const float ax = uj[s] - (float)x0[s], ay = vj[s] - (float)y0[s];
         const float gx = 1.f - ax, gy = 1.f - ay;
-        const float z00 = p.fb / d00, z01 = p.fb / d01, z10 = p.fb / d10, z11 = p.fb / d11;
+        const float z00 = p.cam.fb / d00, z01 = p.cam.fb / d01, z10 = p.cam.fb / d10, z11 = p.cam.fb / d11;
         const float zs = (z00 * gx + z01 * ax) * gy + (z10 * gx + z11 * ax) * ay;
         const float rel = fabsf(zs - Xj[s][2]) / Xj[s][2];
         ++seen;
@@ -119,7 +103,7 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __r
           const float sc = zs / Xj[s][2];
           const float S[3] = {Xj[s][0] * sc, Xj[s][1] * sc, Xj[s][2] * sc};
           float Sw[3];
-          fuse_to_world(R + (frame0 + j) * 9, t + (frame0 + j) * 3, S, Sw);
+          track_to_world(R + (frame0 + j) * 9, t + (frame0 + j) * 3, S, Sw);
 #pragma unroll
           for (int k = 0; k < 3; ++k) acc[k] = acc[k] + Sw[k];
         }
@@ -129,17 +113,17 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __r
       for (int k = 0; k < 3; ++k) pt[k] = acc[k] / (float)views;
       keep = views >= p.min_views && !lower;
       if (interior) {
-        if (fuse_valid(dl) && fuse_valid(dr) && fuse_valid(du) && fuse_valid(dd)) {
+        if (track_valid(dl) && track_valid(dr) && track_valid(du) && track_valid(dd)) {
           float Pl[3], Pr[3], Pu[3], Pd[3];
-          fuse_backproject(dl, u - 1, v, p, Pl);
-          fuse_backproject(dr, u + 1, v, p, Pr);
-          fuse_backproject(du, u, v - 1, p, Pu);
-          fuse_backproject(dd, u, v + 1, p, Pd);
+          track_backproject(dl, u - 1, v, p.cam, Pl);
+          track_backproject(dr, u + 1, v, p.cam, Pr);
+          track_backproject(du, u, v - 1, p.cam, Pu);
+          track_backproject(dd, u, v + 1, p.cam, Pd);
           const float a[3] = {Pr[0] - Pl[0], Pr[1] - Pl[1], Pr[2] - Pl[2]};
           const float c[3] = {Pd[0] - Pu[0], Pd[1] - Pu[1], Pd[2] - Pu[2]};
           float m[3] = {a[1] * c[2] - a[2] * c[1], a[2] * c[0] - a[0] * c[2], a[0] * c[1] - a[1] * c[0]};
           const float len = sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
-          if (len > 0.f && len <= 3.4028234663852886e38f) {
+          if (track_pos_finite(len)) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) m[k] = m[k] / len;
             const float dot = (m[0] * P[0] + m[1] * P[1]) + m[2] * P[2];
@@ -164,44 +148,16 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const float* __r
       normal_o[o] = nrm[k];
     }
   }
-  const unsigned long long mask = __ballot(keep);
-  if ((threadIdx.x & (DIS_WAVE - 1)) == 0) wave_count[threadIdx.x / DIS_WAVE] = __popcll(mask);
-  __syncthreads();
-  if (threadIdx.x == 0) block_count[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+  track_block_count(__popcll(__ballot(keep)), block_count);
 }
 
 // exclusive scan of block_count[0 .. nblocks) -> block_off[0 .. nblocks], block_off[nblocks] the total; count[b] of every track
-__global__ __launch_bounds__(FUSE_SCAN) void fuse_scan_kernel(const int* __restrict__ block_count, int* block_off, int* __restrict__ count,
+__global__ __launch_bounds__(TRACK_SCAN) void fuse_scan_kernel(const int* __restrict__ block_count, int* block_off, int* __restrict__ count,
                                                               int nblocks, int n, int bpt) {
-  __shared__ int wave_sum_s[FUSE_SCAN / DIS_WAVE];
-  const int lane = threadIdx.x & (DIS_WAVE - 1), wid = threadIdx.x / DIS_WAVE;
-  int carry = 0;
-  for (int base = 0; base < nblocks; base += FUSE_SCAN) {
-    const int k = base + threadIdx.x;
-    const int c = k < nblocks ? block_count[k] : 0;
-    int x = c;   // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < DIS_WAVE; o <<= 1) {
-      const int y = __shfl_up(x, o, DIS_WAVE);
-      if (lane >= o) x += y;
-    }
-    if (lane == DIS_WAVE - 1) wave_sum_s[wid] = x;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < FUSE_SCAN / DIS_WAVE; ++q) {
-      const int s = wave_sum_s[q];
-      if (q < wid) before += s;
-      total += s;
-    }
-    if (k < nblocks) block_off[k] = carry + before + (x - c);
-    carry += total;
-    __syncthreads();   // wave_sum_s is rewritten by the next round
-  }
-  if (threadIdx.x == 0) block_off[nblocks] = carry;
+  track_scan(block_count, block_off, nblocks);
   __threadfence();
   __syncthreads();     // the offsets written above by other lanes of this workgroup are read below
-  for (int b = threadIdx.x; b < n; b += FUSE_SCAN) count[b] = block_off[(b + 1) * bpt] - block_off[b * bpt];
+  for (int b = threadIdx.x; b < n; b += TRACK_SCAN) count[b] = block_off[(b + 1) * bpt] - block_off[b * bpt];
 }
 
 __global__ __launch_bounds__(FUSE_BLOCK) void fuse_scatter_kernel(const unsigned char* __restrict__ keep_i, const float* __restrict__ point_i,
@@ -215,12 +171,9 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_scatter_kernel(const unsigned
   const int idx = frame * p.hw + pix;
   const bool keep = pix < p.hw && keep_i[idx] != 0;
   const unsigned long long mask = __ballot(keep);
-  const int lane = threadIdx.x & (DIS_WAVE - 1), wid = threadIdx.x / DIS_WAVE;
-  if (lane == 0) wave_count[wid] = __popcll(mask);
-  __syncthreads();
+  track_wave_counts(__popcll(mask), wave_count);
   if (!keep) return;
-  int rank = block_off[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wid; ++q) rank += wave_count[q];
+  const int rank = track_rank(block_off, wave_count, __popcll(mask & track_lanes_below()));
   if (rank >= p.cap) return;
   const size_t o = (size_t)frame * 3 * p.hw + pix;
 #pragma unroll
@@ -238,26 +191,20 @@ struct FusePlan {
   long off_count, off_off, off_point, off_normal, bytes;   // byte offsets inside the workspace
 };
 
-static inline long fuse_align16(long v) { return (v + 15) & ~15L; }
-
 // false: unsupported extents
 static bool fuse_plan(int n, int tl, int h, int w, FusePlan* pl) {
-  if (n < 1 || tl < 2 || tl > 4 || h < 2 || w < 2 || h > 8192 || w > 8192) return false;
+  if (n < 1 || tl < 2 || tl > TRACK_MAX_TL || !track_image_ok(h, w, 2)) return false;
   pl->pixels = (long)n * tl * h * w;
   if (pl->pixels > 0x7fffffffL) return false;
   pl->bpf = dis_cdiv((long)h * w, FUSE_BLOCK);
   pl->bpt = tl * pl->bpf;
   pl->nblocks = (long)n * pl->bpt;
-  long o = 0;
-  pl->off_count = o;
-  o = fuse_align16(o + pl->nblocks * 4);
-  pl->off_off = o;
-  o = fuse_align16(o + (pl->nblocks + 1) * 4);
-  pl->off_point = o;
-  o = fuse_align16(o + pl->pixels * 12);
-  pl->off_normal = o;
-  o = fuse_align16(o + pl->pixels * 12);
-  pl->bytes = o;
+  TrackCarver ws = {16, 0};
+  pl->off_count = ws.take(pl->nblocks * 4);
+  pl->off_off = ws.take((pl->nblocks + 1) * 4);
+  pl->off_point = ws.take(pl->pixels * 12);
+  pl->off_normal = ws.take(pl->pixels * 12);
+  pl->bytes = ws.off;
   return true;
 }
 
@@ -267,8 +214,6 @@ extern "C" long dis_fuse_workspace(int n, int tl, int h, int w) {
   return pl.bytes;
 }
 
-static inline bool fuse_pos_finite(float v) { return v > 0.f && v <= 3.4028234663852886e38f; }
-
 extern "C" int dis_fuse_track(const float* disp, const float* R, const float* t, const float* K4_host, float baseline, const float* value,
                               float tol, int min_views, int cap, const DisFuseOut* out, int n, int tl, int h, int w, void* workspace,
                               long workspace_bytes, void* stream) {
@@ -277,17 +222,12 @@ extern "C" int dis_fuse_track(const float* disp, const float* R, const float* t,
   if (cap > 0 && (!out->xyz || !out->normal || !out->value || !out->src)) return DIS_ERR_NULL;
   FusePlan pl;
   if (!fuse_plan(n, tl, h, w, &pl)) return DIS_ERR_BAD_SHAPE;
-  const float fx = K4_host[0], fy = K4_host[1], cx = K4_host[2], cy = K4_host[3];
-  if (!(tol > 0.f && tol < 1.f) || min_views < 1 || min_views > tl || !fuse_pos_finite(fx) || !fuse_pos_finite(fy) ||
-      !fuse_pos_finite(baseline) || !(cx >= -3.4028234663852886e38f && cx <= 3.4028234663852886e38f) ||
-      !(cy >= -3.4028234663852886e38f && cy <= 3.4028234663852886e38f) || cap < 0 || workspace_bytes < pl.bytes ||
-      ((uintptr_t)workspace & 15))
-    return DIS_ERR_UNSUPPORTED;
   FuseParams p;
+  if (!(tol > 0.f && tol < 1.f) || min_views < 1 || min_views > tl || !track_camera(K4_host, baseline, &p.cam) || cap < 0 ||
+      workspace_bytes < pl.bytes || ((uintptr_t)workspace & 15))
+    return DIS_ERR_UNSUPPORTED;
   p.n = n, p.tl = tl, p.h = h, p.w = w, p.hw = h * w, p.bpf = pl.bpf;
-  p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy, p.fb = fx * baseline, p.tol = tol;
-  p.min_views = min_views, p.cap = cap;
-  if (!fuse_pos_finite(p.fb)) return DIS_ERR_UNSUPPORTED;
+  p.tol = tol, p.min_views = min_views, p.cap = cap;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
   int* block_count = (int*)(ws + pl.off_count);
@@ -298,7 +238,7 @@ extern "C" int dis_fuse_track(const float* disp, const float* R, const float* t,
   hipLaunchKernelGGL(fuse_check_kernel, dim3(grid), dim3(FUSE_BLOCK), 0, st, disp, R, t, out->views, out->seen, out->keep, out->resid, point,
                      dnormal, block_count, p);
   DIS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(FUSE_SCAN), 0, st, (const int*)block_count, block_off, out->count, (int)pl.nblocks, n,
+  hipLaunchKernelGGL(fuse_scan_kernel, dim3(1), dim3(TRACK_SCAN), 0, st, (const int*)block_count, block_off, out->count, (int)pl.nblocks, n,
                      pl.bpt);
   DIS_CHECK_LAUNCH();
   hipLaunchKernelGGL(fuse_scatter_kernel, dim3(grid), dim3(FUSE_BLOCK), 0, st, (const unsigned char*)out->keep, (const float*)point,

@@ -13,7 +13,7 @@
 //                      6 x 6 system, updates the state - or, in the closing launch, writes R_pair, t_pair and stats, the diagonal included.
 // The first accumulate launch takes the identity instead of reading the state and the first solve launch starts from it, so the
 // workspace needs no initialisation.
-#include "common.h"
+#include "track_common.h"
 
 #define POSE_BLOCK 256
 #define POSE_WAVES (POSE_BLOCK / DIS_WAVE)
@@ -25,10 +25,9 @@
 
 struct PoseParams {
   int n, tl, h, w, hw, bpp;              // bpp = workgroups per pair
-  float fx, fy, cx, cy, fb, s2;          // fb = fx * baseline, s2 = scale * scale
+  TrackCamera cam;
+  float s2;                              // scale * scale
 };
-
-__device__ __forceinline__ bool pose_valid(float d) { return d > 0.f && d <= 3.4028234663852886e38f; }   // finite and > 0 (NaN: false)
 
 __device__ __forceinline__ constexpr int pose_hidx(int p, int q) { return p * 6 - p * (p - 1) / 2 + (q - p); }
 
@@ -72,29 +71,29 @@ __global__ __launch_bounds__(POSE_BLOCK) void pose_accum_kernel(const float* __r
     const float d = di[pix];
     const float uj = (float)u + fl[pix], vj = (float)v + fl[p.hw + pix];
     // (every comparison is false for NaN)
-    const bool in = pose_valid(d) && uj >= 0.f && uj <= (float)(p.w - 1) && vj >= 0.f && vj <= (float)(p.h - 1);
+    const bool in = track_valid(d) && uj >= 0.f && uj <= (float)(p.w - 1) && vj >= 0.f && vj <= (float)(p.h - 1);
     // 0 <= x0 <= w - 2, 0 <= y0 <= h - 2; a pixel without a target reads the cell at the origin and drops it
     const int x0 = in ? min((int)floorf(uj), p.w - 2) : 0;
     const int y0 = in ? min((int)floorf(vj), p.h - 2) : 0;
     const float* c = dj + y0 * p.w + x0;
     const float d00 = c[0], d01 = c[1], d10 = c[p.w], d11 = c[p.w + 1];
-    if (!(in && pose_valid(d00) && pose_valid(d01) && pose_valid(d10) && pose_valid(d11))) continue;   // not matched: nothing is added
+    if (!(in && track_valid(d00) && track_valid(d01) && track_valid(d10) && track_valid(d11))) continue;   // not matched: nothing is added
     const float ax = uj - (float)x0, ay = vj - (float)y0;
     const float gx = 1.f - ax, gy = 1.f - ay;
     const float ds = (d00 * gx + d01 * ax) * gy + (d10 * gx + d11 * ax) * ay;
-    const float z = p.fb / d;
-    const float P0 = z * (((float)u - p.cx) / p.fx), P1 = z * (((float)v - p.cy) / p.fy), P2 = z;
-    const float X0 = ((R[0] * P0 + R[1] * P1) + R[2] * P2) + t[0];
-    const float X1 = ((R[3] * P0 + R[4] * P1) + R[5] * P2) + t[1];
-    const float X2 = ((R[6] * P0 + R[7] * P1) + R[8] * P2) + t[2];
+    float P[3], X[3];
+    track_backproject(d, u, v, p.cam, P);
+    track_to_camera(R, t, P, X);
+    const float X0 = X[0], X1 = X[1], X2 = X[2];
     if (!(X2 > 0.f)) continue;                     // not used
+    // this projection is pose's own: fuse has (fx * X0) / X2 + cx, tsdf fx * (x / zs) + cx, rounded
     const float iz = 1.f / X2;
     const float px = X0 * iz, py = X1 * iz;
-    const float e0 = (p.fx * px + p.cx) - uj, e1 = (p.fy * py + p.cy) - vj, e2 = p.fb * iz - ds;
+    const float e0 = (p.cam.fx * px + p.cam.cx) - uj, e1 = (p.cam.fy * py + p.cam.cy) - vj, e2 = p.cam.fb * iz - ds;
     const float r2 = (e0 * e0 + e1 * e1) + e2 * e2;
     const float g = 1.f / (1.f + r2 / p.s2);
     const float wgt = first ? 1.f : g * g;
-    const float a = p.fx * iz, bb = p.fy * iz, cc = p.fb * iz;
+    const float a = p.cam.fx * iz, bb = p.cam.fy * iz, cc = p.cam.fb * iz;
     const float g0 = -(a * px), g1 = -(bb * py), g2 = -(cc * iz);
     const float J0[5] = {g0 * X1, a * X2 - g0 * X0, -(a * X1), a, g0};
     const float J1[5] = {g1 * X1 - bb * X2, -(g1 * X0), bb * X0, bb, g1};
@@ -262,22 +261,18 @@ struct PosePlan {
   long off_state, off_partial, bytes;
 };
 
-static inline long pose_align16(long v) { return (v + 15) & ~15L; }
-
 // false: unsupported extents
 static bool pose_plan(int n, int tl, int h, int w, PosePlan* pl) {
-  if (n < 1 || tl < 2 || tl > 4 || h < 2 || w < 2 || h > 8192 || w > 8192) return false;
+  if (n < 1 || tl < 2 || tl > TRACK_MAX_TL || !track_image_ok(h, w, 2)) return false;
   if ((long)n * tl * tl * 2 * h * w > 0x7fffffffL) return false;
   pl->pairs = (long)n * tl * tl;
   int bpp = dis_cdiv((long)h * w, 4 * POSE_BLOCK);   // about four pixels per lane, until the cap
   if (bpp > POSE_MAX_BPP) bpp = POSE_MAX_BPP;
   pl->bpp = bpp;
-  long o = 0;
-  pl->off_state = o;
-  o = pose_align16(o + pl->pairs * POSE_STATE * 8);
-  pl->off_partial = o;
-  o = pose_align16(o + pl->pairs * bpp * POSE_REC * 8);
-  pl->bytes = o;
+  TrackCarver ws = {16, 0};
+  pl->off_state = ws.take(pl->pairs * POSE_STATE * 8);
+  pl->off_partial = ws.take(pl->pairs * bpp * POSE_REC * 8);
+  pl->bytes = ws.off;
   return true;
 }
 
@@ -287,24 +282,18 @@ extern "C" long dis_pose_workspace(int n, int tl, int h, int w) {
   return pl.bytes;
 }
 
-static inline bool pose_pos_finite(float v) { return v > 0.f && v <= 3.4028234663852886e38f; }
-static inline bool pose_finite(float v) { return v >= -3.4028234663852886e38f && v <= 3.4028234663852886e38f; }
-
 extern "C" int dis_track_poses(const float* disp, const float* flow, const float* K4_host, float baseline, int iters, float scale,
                                float damping, int min_corr, float* R_pair, float* t_pair, float* stats, int n, int tl, int h, int w,
                                void* workspace, long workspace_bytes, void* stream) {
   if (!disp || !flow || !K4_host || !R_pair || !t_pair || !stats || !workspace) return DIS_ERR_NULL;
   PosePlan pl;
   if (!pose_plan(n, tl, h, w, &pl)) return DIS_ERR_BAD_SHAPE;
-  const float fx = K4_host[0], fy = K4_host[1], cx = K4_host[2], cy = K4_host[3];
-  if (iters < 1 || iters > 64 || !pose_pos_finite(scale) || !(damping >= 0.f && pose_finite(damping)) || min_corr < 6 ||
-      !pose_pos_finite(fx) || !pose_pos_finite(fy) || !pose_pos_finite(baseline) || !pose_finite(cx) || !pose_finite(cy) ||
-      workspace_bytes < pl.bytes || ((uintptr_t)workspace & 15))
-    return DIS_ERR_UNSUPPORTED;
   PoseParams p;
+  p.s2 = scale * scale;
+  if (iters < 1 || iters > 64 || !track_pos_finite(scale) || !(damping >= 0.f && track_finite(damping)) || min_corr < 6 ||
+      !track_camera(K4_host, baseline, &p.cam) || !track_pos_finite(p.s2) || workspace_bytes < pl.bytes || ((uintptr_t)workspace & 15))
+    return DIS_ERR_UNSUPPORTED;
   p.n = n, p.tl = tl, p.h = h, p.w = w, p.hw = h * w, p.bpp = pl.bpp;
-  p.fx = fx, p.fy = fy, p.cx = cx, p.cy = cy, p.fb = fx * baseline, p.s2 = scale * scale;
-  if (!pose_pos_finite(p.fb) || !pose_pos_finite(p.s2)) return DIS_ERR_UNSUPPORTED;
   PoseSolveParams sp;
   sp.tl = tl, sp.bpp = pl.bpp, sp.min_corr = min_corr, sp.damping = (double)damping;
   hipStream_t st = (hipStream_t)stream;

@@ -24,7 +24,7 @@
 // rnd_hit() repeats the setting with a pragma, so that a per-file flag change cannot take the guarantee away.  A zero edge function
 // counts as inside for both; the depth tie-break decides.  The hit depth comes from the plane, z = d0 / (n . ray), not from the edge
 // functions.
-#include "common.h"
+#include "track_common.h"
 #include <math.h>
 
 #define RND_TILE 16
@@ -32,7 +32,6 @@
 #define RND_CAP 1024          // LDS candidate list (ints); flushed when fewer than RND_BLOCK slots are left
 #define RND_MAX_NF (1 << 20)
 #define RND_MAX_NV (1 << 24)
-#define RND_MAX_HW 8192
 #define RND_NEAR 0.05         // camera-frame depth below which a vertex makes its triangle's boxes the whole image
 #define RND_BOX_PAD 0.5       // pixels added to every side of a projected box
 #define RND_SHADOW_EPS 1e-4f  // an occluder counts for ray parameters in (eps, 1 - eps); the hit triangle itself never does
@@ -277,8 +276,7 @@ __global__ void __launch_bounds__(RND_BLOCK) render_cast_kernel(const float4* __
 }
 
 static inline bool rnd_extents_ok(int nv, int nf, int tl, int h, int w) {
-  return nv > 0 && nf > 0 && tl > 0 && h > 0 && w > 0 && tl <= 4 && nf <= RND_MAX_NF && nv <= RND_MAX_NV && h <= RND_MAX_HW &&
-         w <= RND_MAX_HW;
+  return nv > 0 && nf > 0 && tl > 0 && tl <= TRACK_MAX_TL && nf <= RND_MAX_NF && nv <= RND_MAX_NV && track_image_ok(h, w, 1);
 }
 
 extern "C" long dis_render_workspace(int nv, int nf, int tl, int h, int w) {
@@ -295,9 +293,8 @@ extern "C" int dis_render_track(const float* verts, const int* faces, const floa
   RndCam cam;
   cam.fx = K4_host[0]; cam.fy = K4_host[1]; cam.cx = K4_host[2]; cam.cy = K4_host[3];
   cam.baseline = baseline; cam.blend = blend;
-  if (!(cam.fx > 0.f) || !(cam.fy > 0.f) || !isfinite(cam.fx) || !isfinite(cam.fy) || !isfinite(cam.cx) || !isfinite(cam.cy))
-    return DIS_ERR_UNSUPPORTED;
-  if (!(baseline > 0.f) || !isfinite(baseline) || !(blend >= 0.f && blend <= 1.f)) return DIS_ERR_UNSUPPORTED;
+  if (!track_pos_finite(cam.fx) || !track_pos_finite(cam.fy) || !track_finite(cam.cx) || !track_finite(cam.cy)) return DIS_ERR_UNSUPPORTED;
+  if (!track_pos_finite(baseline) || !(blend >= 0.f && blend <= 1.f)) return DIS_ERR_UNSUPPORTED;
   if (((uintptr_t)workspace & 15) != 0) return DIS_ERR_UNSUPPORTED;
   float4* tri = (float4*)workspace;
   int4* box = (int4*)(tri + 4L * tl * nf);

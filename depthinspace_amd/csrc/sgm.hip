@@ -11,7 +11,7 @@
 //                       written without atomics; the first direction stores instead of adding, so S needs no clearing.
 //   sgm_winner_kernel   one wave per pixel (16 consecutive pixels per wave): argmin, second minimum, the right-view argmin read along
 //                       the diagonal of S, validity, parabola; writes every element of disp.
-#include "common.h"
+#include "track_common.h"
 
 typedef unsigned long long sgm_u64;
 typedef unsigned short sgm_u16;
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void sgm_winner_kernel(const sgm_u16* __restri
 }
 
 static inline bool sgm_extents_ok(int n, int h, int w) {
-  return n > 0 && h > 0 && w > 0 && h <= 8192 && w <= 8192 && ((long)n + 1) * h * w <= 0x7fffffffL;
+  return n > 0 && track_image_ok(h, w, 1) && ((long)n + 1) * h * w <= 0x7fffffffL;
 }
 static inline long sgm_census_bytes(int n, int h, int w) { return ((long)n + 1) * h * w * 8; }
 

@@ -20,24 +20,21 @@
 //   tsdf_vertex_kernel     the dense vertex ids (rank or -1) of all cells; an active cell reads its eight corners again (active
 //                          cells are a few per cent of the volume) and writes its vertex at its rank.
 //   tsdf_face_kernel       a quad's two triangles at twice its rank, from the dense vertex ids.
-#include "common.h"
+#include "track_common.h"
 
-#define TSDF_BLOCK 256
-#define TSDF_SCAN 1024
-#define TSDF_MAX_TL 4
-#define TSDF_FLT_MAX 3.4028234663852886e38f
+#define TSDF_BLOCK TRACK_BLOCK
+#define TSDF_MAX_TL TRACK_MAX_TL
 
 struct TsdfParams {
   int tl, h, w, hw, nx, ny, nz, total;   // total = nx ny nz <= 2^30
-  float fx, fy, cx, cy, fb, ox, oy, oz, voxel, trunc;   // fb = fx * baseline
+  TrackCamera cam;
+  float ox, oy, oz, voxel, trunc;
 };
 
 struct MeshParams {
   int nx, ny, nz, total, min_weight, vcap, fcap;
   float ox, oy, oz, voxel;
 };
-
-__device__ __forceinline__ bool tsdf_valid(float d) { return d > 0.f && d <= TSDF_FLT_MAX; }   // finite and > 0 (NaN: false)
 
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_integrate_kernel(const float* __restrict__ disp, const float* __restrict__ R,
                                                                     const float* __restrict__ t, const float* __restrict__ value,
@@ -47,7 +44,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_integrate_kernel(const float*
   if (l >= p.total) return;
   const int i = l % p.nx, r = l / p.nx;
   const int j = r % p.ny, k = r / p.ny;
-  const float X0 = p.ox + (float)i * p.voxel, X1 = p.oy + (float)j * p.voxel, X2 = p.oz + (float)k * p.voxel;
+  const float X[3] = {p.ox + (float)i * p.voxel, p.oy + (float)j * p.voxel, p.oz + (float)k * p.voxel};
   // first every projection and its gather, then the arithmetic
   float zf[TSDF_MAX_TL], df[TSDF_MAX_TL], vf[TSDF_MAX_TL];
   bool in[TSDF_MAX_TL];
@@ -56,19 +53,17 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_integrate_kernel(const float*
     in[f] = false;
     zf[f] = 0.f, df[f] = 0.f, vf[f] = 0.f;
     if (f < p.tl) {
-      const float* Rf = R + f * 9;
-      const float* tf = t + f * 3;
-      const float x = ((Rf[0] * X0 + Rf[1] * X1) + Rf[2] * X2) + tf[0];
-      const float y = ((Rf[3] * X0 + Rf[4] * X1) + Rf[5] * X2) + tf[1];
-      const float z = ((Rf[6] * X0 + Rf[7] * X1) + Rf[8] * X2) + tf[2];
-      const bool front = z > 0.f;
-      const float zs = front ? z : 1.f;
-      const float pu = floorf((p.fx * (x / zs) + p.cx) + 0.5f);
-      const float pv = floorf((p.fy * (y / zs) + p.cy) + 0.5f);
+      float Xc[3];
+      track_to_camera(R + f * 9, t + f * 3, X, Xc);
+      const bool front = Xc[2] > 0.f;
+      const float zs = front ? Xc[2] : 1.f;
+      // this projection is tsdf's own: fuse has (fx * X0) / X2 + cx, pose fx * (X0 * (1 / X2)) + cx, neither rounded
+      const float pu = floorf((p.cam.fx * (Xc[0] / zs) + p.cam.cx) + 0.5f);
+      const float pv = floorf((p.cam.fy * (Xc[1] / zs) + p.cam.cy) + 0.5f);
       // compared as floats before any conversion (every comparison is false for NaN)
       in[f] = front && pu >= 0.f && pu <= (float)(p.w - 1) && pv >= 0.f && pv <= (float)(p.h - 1);
       const int idx = in[f] ? f * p.hw + (int)pv * p.w + (int)pu : 0;   // < tl h w <= 2^28
-      zf[f] = z;
+      zf[f] = Xc[2];
       df[f] = disp[idx];
       vf[f] = value ? value[idx] : 0.f;
     }
@@ -77,8 +72,8 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_integrate_kernel(const float*
   int wt = 0, vc = 0;
 #pragma unroll
   for (int f = 0; f < TSDF_MAX_TL; ++f) {
-    if (!(in[f] && tsdf_valid(df[f]))) continue;
-    const float depth = p.fb / df[f];
+    if (!(in[f] && track_valid(df[f]))) continue;
+    const float depth = p.cam.fb / df[f];
     const float sdf = depth - zf[f];
     if (sdf < -p.trunc) continue;   // behind the surface
     acc = acc + fminf(sdf / p.trunc, 1.f);
@@ -101,7 +96,6 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_flag_kernel(const float* __re
                                                                const MeshParams p) {
   __shared__ float sf[4][TSDF_BLOCK + 4];
   __shared__ unsigned char sw[4][TSDF_BLOCK + 4];
-  __shared__ int wave_count[TSDF_BLOCK / DIS_WAVE];
   const int tid = threadIdx.x;
   const int b0 = blockIdx.x * TSDF_BLOCK;
   const int nxy = p.nx * p.ny;
@@ -148,10 +142,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_flag_kernel(const float* __re
     if (zi && xm && ym && (sf[2][tid] < 0.f) != neg0) f |= 8;
     flags[l] = (unsigned char)f;
   }
-  const unsigned long long mask = __ballot(active);
-  if ((tid & (DIS_WAVE - 1)) == 0) wave_count[tid / DIS_WAVE] = __popcll(mask);
-  __syncthreads();
-  if (tid == 0) block_count[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+  track_block_count(__popcll(__ballot(active)), block_count);
 }
 
 // the quad bits of lattice point l = (i, j, k): bit a is set when the edge along axis a crosses and its four cells are active
@@ -166,55 +157,21 @@ __device__ __forceinline__ unsigned tsdf_quad_bits(const unsigned char* __restri
 
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_quad_kernel(const unsigned char* __restrict__ flags, unsigned char* __restrict__ qmask,
                                                                int* __restrict__ block_count, const MeshParams p) {
-  __shared__ int wave_count[TSDF_BLOCK / DIS_WAVE];
-  const int tid = threadIdx.x;
-  const int l = blockIdx.x * TSDF_BLOCK + tid;
+  const int l = blockIdx.x * TSDF_BLOCK + threadIdx.x;
   unsigned q = 0;
   if (l < p.total) {
     const unsigned f = flags[l];
     if (f & 14) q = tsdf_quad_bits(flags, f, l, p.nx, p.nx * p.ny);   // (a crossing bit implies that the four cells exist)
     qmask[l] = (unsigned char)q;
   }
-  const int cnt = (__popcll(__ballot(q & 1)) + __popcll(__ballot(q & 2))) + __popcll(__ballot(q & 4));
-  if ((tid & (DIS_WAVE - 1)) == 0) wave_count[tid / DIS_WAVE] = cnt;
-  __syncthreads();
-  if (tid == 0) block_count[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+  track_block_count((__popcll(__ballot(q & 1)) + __popcll(__ballot(q & 2))) + __popcll(__ballot(q & 4)), block_count);
 }
 
 // workgroup s: exclusive scan of counts[s][0 .. nblocks) -> offs[s][0 .. nblocks], offs[s][nblocks] the total; count[s] = mul[s] * total
-__global__ __launch_bounds__(TSDF_SCAN) void tsdf_scan_kernel(const int* __restrict__ vcount, const int* __restrict__ qcount, int* voff,
-                                                              int* qoff, int* __restrict__ count, int nblocks) {
-  __shared__ int wave_sum_s[TSDF_SCAN / DIS_WAVE];
-  const int* __restrict__ block_count = blockIdx.x == 0 ? vcount : qcount;
-  int* block_off = blockIdx.x == 0 ? voff : qoff;
-  const int lane = threadIdx.x & (DIS_WAVE - 1), wid = threadIdx.x / DIS_WAVE;
-  int carry = 0;
-  for (int base = 0; base < nblocks; base += TSDF_SCAN) {
-    const int k = base + threadIdx.x;
-    const int c = k < nblocks ? block_count[k] : 0;
-    int x = c;   // inclusive scan inside the wave
-#pragma unroll
-    for (int o = 1; o < DIS_WAVE; o <<= 1) {
-      const int y = __shfl_up(x, o, DIS_WAVE);
-      if (lane >= o) x += y;
-    }
-    if (lane == DIS_WAVE - 1) wave_sum_s[wid] = x;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < TSDF_SCAN / DIS_WAVE; ++q) {
-      const int s = wave_sum_s[q];
-      if (q < wid) before += s;
-      total += s;
-    }
-    if (k < nblocks) block_off[k] = carry + before + (x - c);
-    carry += total;
-    __syncthreads();   // wave_sum_s is rewritten by the next round
-  }
-  if (threadIdx.x == 0) {
-    block_off[nblocks] = carry;
-    count[blockIdx.x] = blockIdx.x == 0 ? carry : 2 * carry;   // two triangles per quad
-  }
+__global__ __launch_bounds__(TRACK_SCAN) void tsdf_scan_kernel(const int* __restrict__ vcount, const int* __restrict__ qcount, int* voff,
+                                                               int* qoff, int* __restrict__ count, int nblocks) {
+  const int total = track_scan(blockIdx.x == 0 ? vcount : qcount, blockIdx.x == 0 ? voff : qoff, nblocks);
+  if (threadIdx.x == 0) count[blockIdx.x] = blockIdx.x == 0 ? total : 2 * total;   // two triangles per quad
 }
 
 __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_vertex_kernel(const float* __restrict__ tsdf, const unsigned char* __restrict__ weight,
@@ -224,14 +181,11 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_vertex_kernel(const float* __
                                                                  float* __restrict__ value, unsigned char* __restrict__ views,
                                                                  int* __restrict__ cell, const MeshParams p) {
   __shared__ int wave_count[TSDF_BLOCK / DIS_WAVE];
-  const int tid = threadIdx.x;
-  const int l = blockIdx.x * TSDF_BLOCK + tid;
+  const int l = blockIdx.x * TSDF_BLOCK + threadIdx.x;
   const bool inside = l < p.total;
   const bool active = inside && (flags[l] & TSDF_F_ACTIVE);
   const unsigned long long mask = __ballot(active);
-  const int lane = tid & (DIS_WAVE - 1), wid = tid / DIS_WAVE;
-  if (lane == 0) wave_count[wid] = __popcll(mask);
-  __syncthreads();
+  track_wave_counts(__popcll(mask), wave_count);
   if (!inside) return;
   const int i = l % p.nx, r = l / p.nx;
   const int j = r % p.ny, k = r / p.ny;
@@ -241,8 +195,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_vertex_kernel(const float* __
     vid[ci] = -1;
     return;
   }
-  int rank = block_off[blockIdx.x] + __popcll(mask & ((1ull << lane) - 1ull));
-  for (int q = 0; q < wid; ++q) rank += wave_count[q];
+  const int rank = track_rank(block_off, wave_count, __popcll(mask & track_lanes_below()));
   vid[ci] = rank;
   if ((unsigned)rank >= (unsigned)p.vcap) return;
   const int nxy = p.nx * p.ny;
@@ -280,7 +233,7 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_vertex_kernel(const float* __
   }
   const float nc = (float)cnt;   // >= 1: the corner signs differ, so an edge crosses
   const float len = sqrtf((g3[0] * g3[0] + g3[1] * g3[1]) + g3[2] * g3[2]);
-  const bool okn = len > 0.f && len <= TSDF_FLT_MAX;
+  const bool okn = track_pos_finite(len);
   const size_t o = (size_t)rank * 3;
   xyz[o] = p.ox + ((float)i + sums[0] / nc) * p.voxel;
   xyz[o + 1] = p.oy + ((float)j + sums[1] / nc) * p.voxel;
@@ -296,17 +249,13 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_face_kernel(const unsigned ch
                                                                const int* __restrict__ block_off, const int* __restrict__ vid,
                                                                int* __restrict__ faces, const MeshParams p) {
   __shared__ int wave_count[TSDF_BLOCK / DIS_WAVE];
-  const int tid = threadIdx.x;
-  const int l = blockIdx.x * TSDF_BLOCK + tid;
+  const int l = blockIdx.x * TSDF_BLOCK + threadIdx.x;
   const unsigned q = l < p.total ? qmask[l] : 0;
   const unsigned long long m0 = __ballot(q & 1), m1 = __ballot(q & 2), m2 = __ballot(q & 4);
-  const int lane = tid & (DIS_WAVE - 1), wid = tid / DIS_WAVE;
-  if (lane == 0) wave_count[wid] = (__popcll(m0) + __popcll(m1)) + __popcll(m2);
-  __syncthreads();
+  track_wave_counts((__popcll(m0) + __popcll(m1)) + __popcll(m2), wave_count);
   if (!q) return;
-  const unsigned long long lower = (1ull << lane) - 1ull;
-  int rank = block_off[blockIdx.x] + (__popcll(m0 & lower) + __popcll(m1 & lower)) + __popcll(m2 & lower);
-  for (int w = 0; w < wid; ++w) rank += wave_count[w];
+  const unsigned long long lower = track_lanes_below();
+  int rank = track_rank(block_off, wave_count, (__popcll(m0 & lower) + __popcll(m1 & lower)) + __popcll(m2 & lower));
   const int i = l % p.nx, r = l / p.nx;
   const int j = r % p.ny, k = r / p.ny;
   const int cx = p.nx - 1, cy = p.ny - 1;
@@ -340,25 +289,24 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_face_kernel(const unsigned ch
   }
 }
 
-static inline bool tsdf_pos_finite(float v) { return v > 0.f && v <= TSDF_FLT_MAX; }
-static inline bool tsdf_finite(float v) { return v >= -TSDF_FLT_MAX && v <= TSDF_FLT_MAX; }
 static inline bool tsdf_grid_ok(int nx, int ny, int nz) {
   return nx >= 2 && ny >= 2 && nz >= 2 && nx <= 1024 && ny <= 1024 && nz <= 1024;
+}
+// false: not a lattice origin
+static inline bool tsdf_origin(const float* origin3_host, float* ox, float* oy, float* oz) {
+  *ox = origin3_host[0], *oy = origin3_host[1], *oz = origin3_host[2];
+  return track_finite(*ox) && track_finite(*oy) && track_finite(*oz);
 }
 
 extern "C" int dis_tsdf_integrate(const float* disp, const float* R, const float* t, const float* K4_host, float baseline, const float* value,
                                   const float* origin3_host, float voxel, float trunc, float* tsdf, unsigned char* weight, float* vvalue,
                                   int tl, int h, int w, int nx, int ny, int nz, void* stream) {
   if (!disp || !R || !t || !K4_host || !origin3_host || !tsdf || !weight || !vvalue) return DIS_ERR_NULL;
-  if (tl < 1 || tl > TSDF_MAX_TL || h < 2 || w < 2 || h > 8192 || w > 8192 || !tsdf_grid_ok(nx, ny, nz)) return DIS_ERR_BAD_SHAPE;
+  if (tl < 1 || tl > TSDF_MAX_TL || !track_image_ok(h, w, 2) || !tsdf_grid_ok(nx, ny, nz)) return DIS_ERR_BAD_SHAPE;
   TsdfParams p;
-  p.fx = K4_host[0], p.fy = K4_host[1], p.cx = K4_host[2], p.cy = K4_host[3];
-  p.ox = origin3_host[0], p.oy = origin3_host[1], p.oz = origin3_host[2];
-  if (!tsdf_pos_finite(voxel) || !tsdf_pos_finite(trunc) || !tsdf_pos_finite(p.fx) || !tsdf_pos_finite(p.fy) || !tsdf_pos_finite(baseline) ||
-      !tsdf_finite(p.cx) || !tsdf_finite(p.cy) || !tsdf_finite(p.ox) || !tsdf_finite(p.oy) || !tsdf_finite(p.oz))
+  if (!track_pos_finite(voxel) || !track_pos_finite(trunc) || !track_camera(K4_host, baseline, &p.cam) ||
+      !tsdf_origin(origin3_host, &p.ox, &p.oy, &p.oz))
     return DIS_ERR_UNSUPPORTED;
-  p.fb = p.fx * baseline;
-  if (!tsdf_pos_finite(p.fb)) return DIS_ERR_UNSUPPORTED;
   p.tl = tl, p.h = h, p.w = w, p.hw = h * w, p.nx = nx, p.ny = ny, p.nz = nz, p.total = nx * ny * nz;
   p.voxel = voxel, p.trunc = trunc;
   hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)dis_cdiv(p.total, TSDF_BLOCK)), dim3(TSDF_BLOCK), 0, (hipStream_t)stream, disp, R, t,
@@ -372,30 +320,21 @@ struct TsdfMeshPlan {
   long off_flags, off_qmask, off_vcount, off_qcount, off_voff, off_qoff, off_vid, bytes;   // byte offsets inside the workspace
 };
 
-static inline long tsdf_align16(long v) { return (v + 15) & ~15L; }
-
 // false: unsupported extents
 static bool tsdf_mesh_plan(int nx, int ny, int nz, TsdfMeshPlan* pl) {
   if (!tsdf_grid_ok(nx, ny, nz)) return false;
   pl->total = (long)nx * ny * nz;
   pl->cells = (long)(nx - 1) * (ny - 1) * (nz - 1);
   pl->nblocks = (pl->total + TSDF_BLOCK - 1) / TSDF_BLOCK;
-  long o = 0;
-  pl->off_flags = o;
-  o = tsdf_align16(o + pl->total);
-  pl->off_qmask = o;
-  o = tsdf_align16(o + pl->total);
-  pl->off_vcount = o;
-  o = tsdf_align16(o + pl->nblocks * 4);
-  pl->off_qcount = o;
-  o = tsdf_align16(o + pl->nblocks * 4);
-  pl->off_voff = o;
-  o = tsdf_align16(o + (pl->nblocks + 1) * 4);
-  pl->off_qoff = o;
-  o = tsdf_align16(o + (pl->nblocks + 1) * 4);
-  pl->off_vid = o;
-  o = tsdf_align16(o + pl->cells * 4);
-  pl->bytes = o;
+  TrackCarver ws = {16, 0};
+  pl->off_flags = ws.take(pl->total);
+  pl->off_qmask = ws.take(pl->total);
+  pl->off_vcount = ws.take(pl->nblocks * 4);
+  pl->off_qcount = ws.take(pl->nblocks * 4);
+  pl->off_voff = ws.take((pl->nblocks + 1) * 4);
+  pl->off_qoff = ws.take((pl->nblocks + 1) * 4);
+  pl->off_vid = ws.take(pl->cells * 4);
+  pl->bytes = ws.off;
   return true;
 }
 
@@ -415,9 +354,8 @@ extern "C" int dis_tsdf_mesh(const float* tsdf, const unsigned char* weight, con
   TsdfMeshPlan pl;
   if (!tsdf_mesh_plan(nx, ny, nz, &pl)) return DIS_ERR_BAD_SHAPE;
   MeshParams p;
-  p.ox = origin3_host[0], p.oy = origin3_host[1], p.oz = origin3_host[2];
-  if (!tsdf_pos_finite(voxel) || !tsdf_finite(p.ox) || !tsdf_finite(p.oy) || !tsdf_finite(p.oz) || min_weight < 1 ||
-      min_weight > TSDF_MAX_TL || vcap < 0 || fcap < 0 || workspace_bytes < pl.bytes || ((uintptr_t)workspace & 15))
+  if (!track_pos_finite(voxel) || !tsdf_origin(origin3_host, &p.ox, &p.oy, &p.oz) || min_weight < 1 || min_weight > TSDF_MAX_TL ||
+      vcap < 0 || fcap < 0 || workspace_bytes < pl.bytes || ((uintptr_t)workspace & 15))
     return DIS_ERR_UNSUPPORTED;
   p.nx = nx, p.ny = ny, p.nz = nz, p.total = (int)pl.total, p.min_weight = min_weight, p.vcap = vcap, p.fcap = fcap, p.voxel = voxel;
   hipStream_t st = (hipStream_t)stream;
@@ -434,7 +372,7 @@ extern "C" int dis_tsdf_mesh(const float* tsdf, const unsigned char* weight, con
   DIS_CHECK_LAUNCH();
   hipLaunchKernelGGL(tsdf_quad_kernel, grid, block, 0, st, (const unsigned char*)flags, qmask, qcount, p);
   DIS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(2), dim3(TSDF_SCAN), 0, st, (const int*)vcount, (const int*)qcount, voff, qoff, out->count,
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(2), dim3(TRACK_SCAN), 0, st, (const int*)vcount, (const int*)qcount, voff, qoff, out->count,
                      (int)pl.nblocks);
   DIS_CHECK_LAUNCH();
   hipLaunchKernelGGL(tsdf_vertex_kernel, grid, block, 0, st, tsdf, weight, vvalue, (const unsigned char*)flags, (const int*)voff, vid, out->xyz,

@@ -22,31 +22,7 @@ import torch
 
 from . import packed, ply
 from .dataset import load_settings
-
-SOURCES = ('gt', 'sgm', 'single_frame', 'multi_frame')
-
-
-def load_track(d, source):
-    """-> disp (tl, H, W), R (tl, 3, 3), t (tl, 3), ambient (tl, H, W), gt disp (tl, H, W) or None: float32 numpy"""
-    if source not in SOURCES:
-        raise ValueError(f'--disp is one of {SOURCES}')
-    with np.load(os.path.join(d, 'frames.npz')) as f:
-        R, t, amb = f['R'], f['t'], f['ambient']
-        gt = f['disp'] if 'disp' in f.files else None
-        disp = None
-        if source in ('gt', 'sgm'):
-            key = 'disp' if source == 'gt' else 'sgm_disp'
-            if key not in f.files:
-                raise ValueError(f'{d}/frames.npz has no array `{key}`')
-            disp = f[key]
-    if disp is None:
-        path = os.path.join(d, f'{source}_disp.npz')
-        if not os.path.exists(path):
-            raise ValueError(f'{path} is missing (data/presave_disp.py writes it)')
-        with np.load(path) as f:
-            disp = f['disp']
-    sq = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape((a.shape[0],) + a.shape[-2:])
-    return sq(disp), np.ascontiguousarray(R, dtype=np.float32), np.ascontiguousarray(t, dtype=np.float32), sq(amb), sq(gt)
+from .trackfiles import SOURCES, load_track, report_text
 
 
 def fuse_arrays(disp, R, t, value, settings, tol=0.01, min_views=2, device='cuda'):
@@ -124,7 +100,7 @@ def fuse_dataset(data_root, source='multi_frame', tol=0.01, min_views=2, force=F
     if acc['gt_n']:
         res['gt_distance'] = acc['gt_sum'] / acc['gt_n']
     print(f'fusion of the {source} disparities over {data_root} (tol {tol:g}, min_views {min_views}): '
-          + '  '.join(f'{k} {v:.6f}' if isinstance(v, float) else f'{k} {v}' for k, v in res.items()))
+          + report_text(res, '.6f'))
     return res
 
 

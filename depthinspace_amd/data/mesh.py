@@ -29,7 +29,7 @@ import torch
 
 from . import packed, ply
 from .dataset import load_settings
-from .fuse import SOURCES, load_track
+from .trackfiles import SOURCES, load_track, report_text
 
 MAX_EXTENT = 1024
 
@@ -164,7 +164,7 @@ def mesh_dataset(data_root, source='multi_frame', res=256, voxel=None, trunc_vox
     if acc['gt_n']:
         res_['gt_depth_error'] = acc['gt_sum'] / acc['gt_n']
     print(f'meshes of the {source} disparities over {data_root} (trunc {trunc_voxels:g} voxels, min_weight {min_weight}): '
-          + '  '.join(f'{k} {v:.6f}' if isinstance(v, float) else f'{k} {v}' for k, v in res_.items()))
+          + report_text(res_, '.6f'))
     return res_
 
 

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import packed
+from .trackfiles import report_text, write_npz
 
 REPORT_THRESHOLDS = (0.5, 1, 2)
 
@@ -39,16 +40,6 @@ def estimate_flows(frames, alpha=1.0, warps=3, iters=64, min_size=8, device='cud
     tl = fr.shape[1]
     flow = ops.dense_flow(torch.from_numpy(fr).to(torch.device(device)), alpha, warps, iters, min_size).cpu().numpy()
     return {f'flow_{i}{j}': np.ascontiguousarray(flow[:, i * tl + j]) for i, j in pair_keys(tl)}
-
-
-def _write_atomically(path, arrays):
-    tmp = path + '.tmp.npz'   # (np.savez appends .npz to any other ending)
-    try:
-        np.savez(tmp, **arrays)
-        os.replace(tmp, path)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
 
 
 def _frames_of(d, source):
@@ -90,14 +81,14 @@ def presave_flow(data_root, source='ambient', alpha=1.0, warps=3, iters=64, min_
     data_root = str(data_root)
     if report:
         res = flow_report(data_root, source, alpha, warps, iters, min_size, device)
-        print(f'flow estimate against the stored flows over {data_root}: ' + '  '.join(f'{k} {v:.4f}' for k, v in res.items()))
+        print(f'flow estimate against the stored flows over {data_root}: ' + report_text(res, '.4f'))
         return res
     done = 0
     for d in packed.track_dirs(data_root):
         path = os.path.join(d, 'flow.npz')
         if os.path.exists(path) and not force:
             continue
-        _write_atomically(path, estimate_flows(_frames_of(d, source), alpha, warps, iters, min_size, device))
+        write_npz(path, estimate_flows(_frames_of(d, source), alpha, warps, iters, min_size, device))
         done += 1
     if pack:
         packed.pack_dataset(data_root)

@@ -31,29 +31,9 @@ import torch
 
 from . import packed
 from .dataset import load_settings
-from .fuse import SOURCES
+from .trackfiles import SOURCES, load_disp, report_text, rewrite_npz
 
 BATCH = 4
-
-
-def load_disp(d, source):
-    """the disparities (tl, H, W) float32 of one track, by the rules of data/fuse.py's load_track: `disp` (gt) or `sgm_disp` (sgm) of
-    frames.npz, or the `disp` of single_frame_disp.npz / multi_frame_disp.npz"""
-    if source not in SOURCES:
-        raise ValueError(f'--disp is one of {SOURCES}')
-    if source in ('gt', 'sgm'):
-        key = 'disp' if source == 'gt' else 'sgm_disp'
-        with np.load(os.path.join(d, 'frames.npz')) as f:
-            if key not in f.files:
-                raise ValueError(f'{d}/frames.npz has no array `{key}`')
-            disp = f[key]
-    else:
-        path = os.path.join(d, f'{source}_disp.npz')
-        if not os.path.exists(path):
-            raise ValueError(f'{path} is missing (data/presave_disp.py writes it)')
-        with np.load(path) as f:
-            disp = f['disp']
-    return np.ascontiguousarray(disp, dtype=np.float32).reshape((disp.shape[0],) + disp.shape[-2:])
 
 
 def load_flow(d, tl):
@@ -155,20 +135,6 @@ def report_line(acc):
     return res
 
 
-def _rewrite_with(path, extra):
-    """frames.npz plus (or with other) arrays `extra`: the other arrays are copied as they are; temporary file, then os.replace"""
-    with np.load(path) as f:
-        arrays = {k: f[k] for k in f.files}
-    arrays.update(extra)
-    tmp = path + '.tmp.npz'   # (np.savez appends .npz to any other ending)
-    try:
-        np.savez(tmp, **arrays)
-        os.replace(tmp, path)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-
-
 def estimate_pairs(disps, flows, settings, iters=6, scale=1.0, damping=0.0, min_corr=64, device='cuda'):
     """lists of (tl, H, W) disparities and (tl tl, 2, H, W) flows of tracks of one length, float32 numpy -> R_pair (n, tl, tl, 3, 3),
     t_pair (n, tl, tl, 3), stats (n, tl, tl, 4) float32 numpy (one call of ops.track_poses)"""
@@ -218,7 +184,7 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
             if poses is None:
                 failed.append(d)
                 continue
-            _rewrite_with(os.path.join(d, 'frames.npz'), {'R': poses[0], 't': poses[1]})
+            rewrite_npz(os.path.join(d, 'frames.npz'), {'R': poses[0], 't': poses[1]})
             done += 1
     if failed:
         print(f'{len(failed)} tracks failed (a frame without an estimated pair with frame 0) and were left as they are: '
@@ -230,7 +196,7 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
     res = report_line(acc) if acc else {}
     res.update(tracks=len(todo), written=done, failed_tracks=len(failed))
     print(f'poses from the {source} disparities over {data_root} (iters {iters}, scale {scale:g}, damping {damping:g}): '
-          + '  '.join(f'{key} {v:.6g}' if isinstance(v, float) else f'{key} {v}' for key, v in res.items()))
+          + report_text(res, '.6g'))
     return res
 
 

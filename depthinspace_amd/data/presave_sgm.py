@@ -20,6 +20,7 @@ import torch
 
 from .dataset import load_settings
 from . import packed
+from .trackfiles import rewrite_npz
 
 REPORT_THRESHOLDS = (0.1, 0.5, 1, 2, 5)
 
@@ -31,20 +32,6 @@ def match_frames(im, pattern, ndisp=64, p1=7, p2=60, uniq=5, lr=1, device='cuda'
     d = ops.sgm_disparity(torch.from_numpy(np.ascontiguousarray(im, dtype=np.float32)).to(dev),
                           torch.from_numpy(np.ascontiguousarray(pattern, dtype=np.float32)).to(dev), ndisp, p1, p2, uniq, lr)
     return d.cpu().numpy()
-
-
-def _rewrite_with(path, name, value):
-    """frames.npz plus one array: the other arrays are copied as they are; temporary file, then os.replace"""
-    with np.load(path) as f:
-        arrays = {k: f[k] for k in f.files}
-    arrays[name] = value
-    tmp = path + '.tmp.npz'   # (np.savez appends .npz to any other ending)
-    try:
-        np.savez(tmp, **arrays)
-        os.replace(tmp, path)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
 
 
 def sgm_report(data_root):
@@ -82,7 +69,7 @@ def presave_sgm(data_root, ndisp=64, p1=7, p2=60, uniq=5, lr=1, report=False, pa
                 continue
             im = f['im']
         sgm = np.asarray(match_frames(im, pattern, ndisp, p1, p2, uniq, lr, device), dtype=np.float32).reshape(im.shape)
-        _rewrite_with(path, 'sgm_disp', sgm)
+        rewrite_npz(path, {'sgm_disp': sgm})
         done += 1
     if pack:
         packed.pack_dataset(data_root)

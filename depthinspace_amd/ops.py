@@ -29,6 +29,44 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+# the parts the wrappers of the track tools share (render_track ... tsdf_mesh, at the end of this file)
+def _fin(v):
+    return v == v and abs(v) < float('inf')
+
+
+def _k4(K):
+    """fx, fy, cx, cy of the 3 x 3 host intrinsics K (numpy or a CPU tensor), as floats"""
+    return [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
+
+
+def _workspace(name, need, workspace, dev):
+    """a fresh workspace of `need` bytes, or the caller's once it is a contiguous uint8 device tensor (else RuntimeError) of at
+    least `need` bytes at a 16-byte boundary (else DisHipError)"""
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise RuntimeError(f'{name}: workspace must be a contiguous uint8 CUDA(HIP) tensor')
+    if workspace.numel() < need or workspace.data_ptr() % 16:
+        raise lib.DisHipError(f'{name}: workspace must hold at least {need} bytes and be 16-byte aligned')
+    return workspace
+
+
+def _out_struct(cls, tensors):
+    """the ctypes out-struct `cls` with the address of tensors[field] in every field; NULL for a field without a tensor, or with an
+    empty one"""
+    O = cls()
+    for f, _ in cls._fields_:
+        setattr(O, f, (tensors[f].data_ptr() or None) if f in tensors else None)
+    return O
+
+
+def _track_dims(name, x, what='disp', verb='is'):
+    """n, tl, H, W of the maps x (n, tl, H, W) or (n, tl, 1, H, W)"""
+    if not (x.dim() == 4 or (x.dim() == 5 and x.shape[2] == 1)):
+        raise RuntimeError(f'{name}: {what} (n, tl, H, W) or (n, tl, 1, H, W) {verb} expected')
+    return int(x.shape[0]), int(x.shape[1]), int(x.shape[-2]), int(x.shape[-1])
+
+
 # Zeroed fp64 accumulators (GroupNorm statistics, loss sums) come from one arena per device that is cleared ONCE per
 # step (begin_step, called by FlatAdam.zero_grad) instead of one tiny fill kernel per accumulator (~100 per step).
 # A slice is handed out at most once between two clears; without begin_step (tests, inference) the arena simply runs
@@ -2702,10 +2740,7 @@ def render_track(verts, faces, albedo, R, t, K, baseline, blend, pattern, want_i
     if need < 0:
         raise lib.DisHipError(f'dis_render_workspace: unsupported extents nv={nv} nf={nf} tl={tl} h={h} w={w}')
     dev = verts.device
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= need):
-        raise RuntimeError(f'render_track: workspace must be a contiguous uint8 CUDA(HIP) tensor of at least {need} bytes')
+    workspace = _workspace('render_track', need, workspace, dev)
     res = {'im': torch.empty((tl, 1, h, w), dtype=torch.float32, device=dev),
            'ambient': torch.empty((tl, 1, h, w), dtype=torch.float32, device=dev),
            'disp': torch.empty((tl, 1, h, w), dtype=torch.float32, device=dev),
@@ -2713,12 +2748,9 @@ def render_track(verts, faces, albedo, R, t, K, baseline, blend, pattern, want_i
     if want_ids:
         res['tri_id'] = torch.empty((tl, h, w), dtype=torch.int32, device=dev)
         res['lit'] = torch.empty((tl, h, w), dtype=torch.float32, device=dev)
-    O = lib.RenderOut()
-    for f, _ in lib.RenderOut._fields_:
-        setattr(O, f, res[f].data_ptr() if f in res else None)
-    K4 = lib.host_floats([K[0][0], K[1][1], K[0][2], K[1][2]])
-    lib.call('dis_render_track', verts, faces, albedo, nv, nf, R, t, K4, float(baseline), float(blend), pattern, _ct.addressof(O),
-             tl, h, w, workspace)
+    O = _out_struct(lib.RenderOut, res)
+    lib.call('dis_render_track', verts, faces, albedo, nv, nf, R, t, lib.host_floats(_k4(K)), float(baseline), float(blend), pattern,
+             _ct.addressof(O), tl, h, w, workspace)
     return res
 
 
@@ -2741,10 +2773,7 @@ def sgm_disparity(im, pattern, ndisp=64, p1=7, p2=60, uniq=5, lr=1, want_debug=F
     if not (0 < p1 < p2 <= 127 and 0 <= uniq < 100 and lr >= 0):   # refused before anything is allocated or launched
         raise lib.DisHipError(f'sgm_disparity: unsupported configuration p1={p1} p2={p2} uniq={uniq} lr={lr}')
     dev = im.device
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous() and workspace.numel() >= need):
-        raise RuntimeError(f'sgm_disparity: workspace must be a contiguous uint8 CUDA(HIP) tensor of at least {need} bytes')
+    workspace = _workspace('sgm_disparity', need, workspace, dev)
     disp = torch.empty_like(im)
     dbg = None
     if want_debug:
@@ -2777,9 +2806,7 @@ def dense_flow(frames, alpha=1.0, warps=3, iters=64, min_size=8, workspace=None,
     values, for scripts/flow_rate.py.  The inputs are data: no autograd.  workspace: an optional uint8 tensor of at least
     dis_flow_workspace(...) bytes to reuse between calls (and what makes the call capturable without an allocation)."""
     _chk(frames)
-    if not (frames.dim() == 4 or (frames.dim() == 5 and frames.shape[2] == 1)):
-        raise RuntimeError('dense_flow: frames (n, tl, H, W) or (n, tl, 1, H, W) are expected')
-    n, tl, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[-2]), int(frames.shape[-1])
+    n, tl, h, w = _track_dims('dense_flow', frames, 'frames', 'are')
     alpha, warps, iters, min_size = float(alpha), int(warps), int(iters), int(min_size)
     need = lib.fn('dis_flow_workspace')(n, tl, h, w, min_size)
     if need < 0:
@@ -2790,13 +2817,8 @@ def dense_flow(frames, alpha=1.0, warps=3, iters=64, min_size=8, workspace=None,
         raise lib.DisHipError(f'dense_flow: unsupported configuration alpha={alpha} warps={warps} iters={iters} variant={variant} '
                               f'debug_level={debug_level}')
     dev = frames.device
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-        raise RuntimeError('dense_flow: workspace must be a contiguous uint8 CUDA(HIP) tensor')
-    elif workspace.numel() < need or workspace.data_ptr() % 16:
-        raise lib.DisHipError(f'dense_flow: workspace must hold at least {need} bytes and be 16-byte aligned')
-    flow = torch.empty((n, tl * tl, 2, h, w), dtype=torch.float32, device=dev)
+    workspace = _workspace('dense_flow', need, workspace, dev)
+    flow =torch.empty((n, tl * tl, 2, h, w), dtype=torch.float32, device=dev)
     D = lib.FlowDebug()
     D.level, D.variant = int(debug_level), int(variant)
     bufs = None
@@ -2840,9 +2862,7 @@ def fuse_track(disp, R, t, K, baseline, value=None, tol=0.01, min_views=2, cap=N
     _chk(disp, R, t)
     if value is not None:
         _chk(value)
-    if not (disp.dim() == 4 or (disp.dim() == 5 and disp.shape[2] == 1)):
-        raise RuntimeError('fuse_track: disp (n, tl, H, W) or (n, tl, 1, H, W) is expected')
-    n, tl, h, w = int(disp.shape[0]), int(disp.shape[1]), int(disp.shape[-2]), int(disp.shape[-1])
+    n, tl, h, w = _track_dims('fuse_track', disp)
     if tuple(R.shape) != (n, tl, 3, 3) or tuple(t.shape) != (n, tl, 3):
         raise RuntimeError('fuse_track: R (n, tl, 3, 3) and t (n, tl, 3) are expected')
     if value is not None and (value.numel() != disp.numel() or tuple(value.shape[:2]) != (n, tl) or tuple(value.shape[-2:]) != (h, w)):
@@ -2851,20 +2871,14 @@ def fuse_track(disp, R, t, K, baseline, value=None, tol=0.01, min_views=2, cap=N
     if need < 0:
         raise lib.DisHipError(f'dis_fuse_workspace: unsupported extents n={n} tl={tl} h={h} w={w}')
     tol, min_views, baseline = float(tol), int(min_views), float(baseline)
-    K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
+    K4 = _k4(K)
     total = n * tl * h * w
     cap = total if cap is None else int(cap)
-    fin = lambda v: v == v and abs(v) < float('inf')
-    if not (0.0 < tol < 1.0 and 1 <= min_views <= tl and cap >= 0 and all(fin(v) for v in K4) and K4[0] > 0 and K4[1] > 0
-            and fin(baseline) and baseline > 0):   # refused before anything is allocated or launched
+    if not (0.0 < tol < 1.0 and 1 <= min_views <= tl and cap >= 0 and all(_fin(v) for v in K4) and K4[0] > 0 and K4[1] > 0
+            and _fin(baseline) and baseline > 0):   # refused before anything is allocated or launched
         raise lib.DisHipError(f'fuse_track: unsupported configuration tol={tol} min_views={min_views} cap={cap} K={K4} baseline={baseline}')
     dev = disp.device
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-        raise RuntimeError('fuse_track: workspace must be a contiguous uint8 CUDA(HIP) tensor')
-    elif workspace.numel() < need or workspace.data_ptr() % 16:
-        raise lib.DisHipError(f'fuse_track: workspace must hold at least {need} bytes and be 16-byte aligned')
+    workspace = _workspace('fuse_track', need, workspace, dev)
     res = {'xyz': torch.empty((cap, 3), dtype=torch.float32, device=dev), 'normal': torch.empty((cap, 3), dtype=torch.float32, device=dev),
            'value': torch.empty((cap,), dtype=torch.float32, device=dev), 'src': torch.empty((cap,), dtype=torch.int32, device=dev),
            'count': torch.empty((n,), dtype=torch.int32, device=dev)}
@@ -2873,10 +2887,7 @@ def fuse_track(disp, R, t, K, baseline, value=None, tol=0.01, min_views=2, cap=N
     if want_dense:
         dense['point'] = torch.empty((n, tl, 3, h, w), dtype=torch.float32, device=dev)
         dense['dnormal'] = torch.empty((n, tl, 3, h, w), dtype=torch.float32, device=dev)
-    O = lib.FuseOut()
-    for f, _ in lib.FuseOut._fields_:
-        src_ = res if f in res else dense
-        setattr(O, f, (src_[f].data_ptr() or None) if f in src_ else None)
+    O = _out_struct(lib.FuseOut, {**res, **dense})
     lib.call('dis_fuse_track', disp, R, t, lib.host_floats(K4), baseline, value, tol, min_views, cap, _ct.addressof(O), n, tl, h, w,
              workspace, int(workspace.numel()))
     if want_dense:
@@ -2901,28 +2912,20 @@ def track_poses(disp, flow, K, baseline, iters=6, scale=1.0, damping=0.0, min_co
     dis_pose_workspace(...) bytes to reuse between calls (and what makes the call capturable without an allocation besides the
     outputs)."""
     _chk(disp, flow)
-    if not (disp.dim() == 4 or (disp.dim() == 5 and disp.shape[2] == 1)):
-        raise RuntimeError('track_poses: disp (n, tl, H, W) or (n, tl, 1, H, W) is expected')
-    n, tl, h, w = int(disp.shape[0]), int(disp.shape[1]), int(disp.shape[-2]), int(disp.shape[-1])
+    n, tl, h, w = _track_dims('track_poses', disp)
     if tuple(flow.shape) != (n, tl * tl, 2, h, w):
         raise RuntimeError('track_poses: flow (n, tl * tl, 2, H, W) is expected')
     need = lib.fn('dis_pose_workspace')(n, tl, h, w)
     if need < 0:
         raise lib.DisHipError(f'dis_pose_workspace: unsupported extents n={n} tl={tl} h={h} w={w}')
     iters, scale, damping, min_corr, baseline = int(iters), float(scale), float(damping), int(min_corr), float(baseline)
-    K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
-    fin = lambda v: v == v and abs(v) < float('inf')
-    if not (1 <= iters <= 64 and fin(scale) and scale > 0 and fin(damping) and damping >= 0 and min_corr >= 6 and all(fin(v) for v in K4)
-            and K4[0] > 0 and K4[1] > 0 and fin(baseline) and baseline > 0):   # refused before anything is allocated or launched
+    K4 = _k4(K)
+    if not (1 <= iters <= 64 and _fin(scale) and scale > 0 and _fin(damping) and damping >= 0 and min_corr >= 6 and all(_fin(v) for v in K4)
+            and K4[0] > 0 and K4[1] > 0 and _fin(baseline) and baseline > 0):   # refused before anything is allocated or launched
         raise lib.DisHipError(f'track_poses: unsupported configuration iters={iters} scale={scale} damping={damping} min_corr={min_corr} '
                               f'K={K4} baseline={baseline}')
     dev = disp.device
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-        raise RuntimeError('track_poses: workspace must be a contiguous uint8 CUDA(HIP) tensor')
-    elif workspace.numel() < need or workspace.data_ptr() % 16:
-        raise lib.DisHipError(f'track_poses: workspace must hold at least {need} bytes and be 16-byte aligned')
+    workspace = _workspace('track_poses', need, workspace, dev)
     res = {'R_pair': torch.empty((n, tl, tl, 3, 3), dtype=torch.float32, device=dev),
            't_pair': torch.empty((n, tl, tl, 3), dtype=torch.float32, device=dev),
            'stats': torch.empty((n, tl, tl, 4), dtype=torch.float32, device=dev)}
@@ -2934,10 +2937,6 @@ def track_poses(disp, flow, K, baseline, iters=6, scale=1.0, damping=0.0, min_co
 # ----------------------------------------------------------------------------------------------------------------------
 # volumetric fusion (csrc/tsdf.hip; data/mesh.py writes the meshes)
 # ----------------------------------------------------------------------------------------------------------------------
-def _tsdf_fin(v):
-    return v == v and abs(v) < float('inf')
-
-
 def tsdf_integrate(disp, R, t, K, baseline, value=None, *, origin, voxel, trunc, grid):
     """dis_tsdf_integrate: the disparity maps disp (tl, H, W) or (tl, 1, H, W) of ONE track, 1 <= tl <= 4, with the poses R (tl, 3, 3),
     t (tl, 3) (X_c = R X_w + t), intrinsics K (3 x 3, host) and the baseline -> a truncated signed distance volume on the lattice
@@ -2960,10 +2959,10 @@ def tsdf_integrate(disp, R, t, K, baseline, value=None, *, origin, voxel, trunc,
     nx, ny, nz = (int(g) for g in grid)
     voxel, trunc, baseline = float(voxel), float(trunc), float(baseline)
     origin = [float(origin[0]), float(origin[1]), float(origin[2])]
-    K4 = [float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])]
+    K4 = _k4(K)
     if not (1 <= tl <= 4 and 2 <= h <= 8192 and 2 <= w <= 8192 and all(2 <= g <= 1024 for g in (nx, ny, nz))):
         raise lib.DisHipError(f'tsdf_integrate: unsupported extents tl={tl} h={h} w={w} grid={(nx, ny, nz)}')
-    if not (all(_tsdf_fin(v) for v in K4 + origin + [voxel, trunc, baseline]) and voxel > 0 and trunc > 0 and K4[0] > 0 and K4[1] > 0
+    if not (all(_fin(v) for v in K4 + origin + [voxel, trunc, baseline]) and voxel > 0 and trunc > 0 and K4[0] > 0 and K4[1] > 0
             and baseline > 0):   # refused before anything is allocated or launched
         raise lib.DisHipError(f'tsdf_integrate: unsupported configuration voxel={voxel} trunc={trunc} origin={origin} K={K4} '
                               f'baseline={baseline}')
@@ -3001,17 +3000,12 @@ def tsdf_mesh(tsdf, weight, vvalue, origin, voxel, min_weight=1, vcap=None, fcap
         raise lib.DisHipError(f'dis_tsdf_mesh_workspace: unsupported extents nx={nx} ny={ny} nz={nz}')
     voxel, min_weight = float(voxel), int(min_weight)
     origin = [float(origin[0]), float(origin[1]), float(origin[2])]
-    if not (all(_tsdf_fin(v) for v in origin + [voxel]) and voxel > 0 and 1 <= min_weight <= 4
+    if not (all(_fin(v) for v in origin + [voxel]) and voxel > 0 and 1 <= min_weight <= 4
             and (vcap is None or int(vcap) >= 0) and (fcap is None or int(fcap) >= 0)):   # refused before anything is allocated or launched
         raise lib.DisHipError(f'tsdf_mesh: unsupported configuration voxel={voxel} origin={origin} min_weight={min_weight} vcap={vcap} '
                               f'fcap={fcap}')
     dev = tsdf.device
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-        raise RuntimeError('tsdf_mesh: workspace must be a contiguous uint8 CUDA(HIP) tensor')
-    elif workspace.numel() < need or workspace.data_ptr() % 16:
-        raise lib.DisHipError(f'tsdf_mesh: workspace must hold at least {need} bytes and be 16-byte aligned')
+    workspace = _workspace('tsdf_mesh', need, workspace, dev)
     origin_h = lib.host_floats(origin)
 
     def run(vc, fc, dense):
@@ -3021,9 +3015,7 @@ def tsdf_mesh(tsdf, weight, vvalue, origin, voxel, min_weight=1, vcap=None, fcap
                'count': torch.empty((2,), dtype=torch.int32, device=dev)}
         if dense:
             res['vid'] = torch.empty((nz - 1, ny - 1, nx - 1), dtype=torch.int32, device=dev)
-        O = lib.TsdfMeshOut()
-        for f, _ in lib.TsdfMeshOut._fields_:
-            setattr(O, f, (res[f].data_ptr() or None) if f in res else None)
+        O = _out_struct(lib.TsdfMeshOut, res)
         lib.call('dis_tsdf_mesh', tsdf, weight, vvalue, origin_h, voxel, min_weight, vc, fc, _ct.addressof(O), nx, ny, nz, workspace,
                  int(workspace.numel()))
         return res

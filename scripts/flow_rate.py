@@ -24,6 +24,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import rate_common as RC   # noqa: E402
+
 
 def level_sizes(h, w, min_size):
     from depthinspace_amd import ops
@@ -58,10 +60,7 @@ def main(argv=None):
     ap.add_argument('--warps', type=int, default=3)
     ap.add_argument('--iters', type=int, default=64)
     ap.add_argument('--min-size', type=int, default=8)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--repeats', type=int, default=9)
-    ap.add_argument('--calls', type=int, default=3)
-    ap.add_argument('--json', default=None, help='also write the result lines to this file')
+    RC.add_timing_args(ap, calls=3)
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -75,18 +74,7 @@ def main(argv=None):
     ws = torch.empty(lib.fn('dis_flow_workspace')(a.n, a.tl, a.h, a.w, a.min_size), dtype=torch.uint8, device='cuda')
     lines, flows = [], []
     for variant in (0, 1):
-        for _ in range(a.warmup):
-            flow = ops.dense_flow(frames, workspace=ws, variant=variant, **kw)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.calls):
-                flow = ops.dense_flow(frames, workspace=ws, variant=variant, **kw)
-            e1.record()
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.calls)
+        ms, flow = RC.eager(lambda: ops.dense_flow(frames, workspace=ws, variant=variant, **kw), a.warmup, a.repeats, a.calls)
         flows.append(flow)
         med = statistics.median(ms)
         model = byte_model(a.n, a.tl, a.h, a.w, a.warps, a.iters, a.min_size, variant)
@@ -101,8 +89,7 @@ def main(argv=None):
                     true.append(np.sqrt((t ** 2).sum(1)).mean())
         res = {'h': a.h, 'w': a.w, 'n': a.n, 'tl': a.tl, 'variant': variant, **kw, 'levels': len(level_sizes(a.h, a.w, a.min_size)),
                'launches': launches(a.h, a.w, a.warps, a.iters, a.min_size, variant),
-               'call_ms_median': round(med, 4), 'call_ms_min': round(min(ms), 4), 'call_ms_max': round(max(ms), 4),
-               'tracks_per_s': round(a.n / med * 1e3, 2), 'pairs_per_s': round(a.n * a.tl * (a.tl - 1) / med * 1e3, 1),
+               **RC.ms_fields('call_ms', ms), 'tracks_per_s': round(a.n / med * 1e3, 2), 'pairs_per_s': round(a.n * a.tl * (a.tl - 1) / med * 1e3, 1),
                'model_bytes': total, 'model_bytes_by_family': model, 'achieved_GB_per_s': round(total / med / 1e6, 1),
                'workspace_bytes': int(ws.numel()), 'mean_true_flow_px': round(float(np.mean(true)), 3),
                'mean_end_point_error_px': round(float(np.mean(err)), 4)}
@@ -110,9 +97,7 @@ def main(argv=None):
         lines.append(res)
     same = bool(torch.equal(flows[0], flows[1]))
     print(json.dumps({'variants_give_the_same_bits': same, 'speedup_of_variant_0': round(lines[1]['call_ms_median'] / lines[0]['call_ms_median'], 3)}))
-    if a.json:
-        with open(a.json, 'w') as fp:
-            json.dump(lines + [{'variants_give_the_same_bits': same}], fp, indent=1)
+    RC.emit(lines + [{'variants_give_the_same_bits': same}], a.json)
 
 
 if __name__ == '__main__':

@@ -25,7 +25,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-HBM_BYTES_PER_S = 8e12
+from rate_common import HBM_BYTES_PER_S, add_timing_args, emit, time_call, timing_fields   # noqa: E402
 
 
 def byte_model(pixels, kept):
@@ -41,10 +41,7 @@ def main(argv=None):
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 4], help='tracks per call')
     ap.add_argument('--tol', type=float, default=0.01)
     ap.add_argument('--min-views', type=int, default=2)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--repeats', type=int, default=9)
-    ap.add_argument('--calls', type=int, default=50)
-    ap.add_argument('--json', default=None, help='also write the result lines to this file')
+    add_timing_args(ap)
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -61,34 +58,7 @@ def main(argv=None):
         disp, R, t, val = up(disp_h), up(batch['R']), up(batch['t']), up(batch['ambient0'][:, :, 0])
         ws = torch.empty(lib.fn('dis_fuse_workspace')(n, a.tl, a.h, a.w), dtype=torch.uint8, device='cuda')
         call = lambda: ops.fuse_track(disp, R, t, st.K, st.baseline, val, tol=a.tol, min_views=a.min_views, workspace=ws)
-        for _ in range(a.warmup):
-            r = call()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.calls):
-                r = call()
-            e1.record()
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.calls)
-        med = statistics.median(ms)
-        side = torch.cuda.Stream()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            rg = call()
-        gms = []
-        for k in range(a.repeats + 1):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.calls):
-                graph.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            if k:                                  # the first window is the warm-up
-                gms.append(e0.elapsed_time(e1) / a.calls)
+        ms, gms, r, rg = time_call(call, a.warmup, a.repeats, a.calls)
         gmed = statistics.median(gms)
         kept = int(r['count'].sum().item())
         same = all(bool(torch.equal(rg[k][:kept] if k != 'count' else rg[k], r[k][:kept] if k != 'count' else r[k])) for k in r)
@@ -96,9 +66,7 @@ def main(argv=None):
         model = byte_model(pixels, kept)
         total = sum(model.values())
         res = {'h': a.h, 'w': a.w, 'n': n, 'tl': a.tl, 'tol': a.tol, 'min_views': a.min_views, 'launches': 3,
-               'call_ms_median': round(med, 4), 'call_ms_min': round(min(ms), 4), 'call_ms_max': round(max(ms), 4),
-               'tracks_per_s': round(n / med * 1e3, 1), 'graph_ms_median': round(gmed, 4), 'graph_ms_min': round(min(gms), 4),
-               'graph_ms_max': round(max(gms), 4), 'graph_tracks_per_s': round(n / gmed * 1e3, 1), 'graph_equals_eager': same,
+               **timing_fields(n, ms, gms), 'graph_equals_eager': same,
                'pixels': pixels, 'kept': kept, 'model_bytes': total, 'model_bytes_by_launch': model,
                'achieved_GB_per_s': round(total / gmed / 1e6, 1), 'share_of_hbm': round(total / (gmed * 1e-3) / HBM_BYTES_PER_S, 4),
                'model_ms_at_hbm': round(total / HBM_BYTES_PER_S * 1e3, 4), 'workspace_bytes': int(ws.numel())}
@@ -111,9 +79,7 @@ def main(argv=None):
             res['src_equal_to_numpy'] = bool(np.array_equal(ref['src'], r['src'][:kept].cpu().numpy()))
         print(json.dumps(res))
         lines.append(res)
-    if a.json:
-        with open(a.json, 'w') as fp:
-            json.dump(lines, fp, indent=1)
+    emit(lines, a.json)
 
 
 if __name__ == '__main__':

@@ -24,7 +24,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-HBM_BYTES_PER_S = 8e12
+from rate_common import HBM_BYTES_PER_S, add_timing_args, emit, time_call, timing_fields   # noqa: E402
 
 
 def byte_model(n, tl, h, w, iters, workspace_bytes):
@@ -40,10 +40,7 @@ def main(argv=None):
     ap.add_argument('--tl', type=int, default=4)
     ap.add_argument('--iters', type=int, default=6)
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 4], help='tracks per call')
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--repeats', type=int, default=9)
-    ap.add_argument('--calls', type=int, default=50)
-    ap.add_argument('--json', default=None, help='also write the result lines to this file')
+    add_timing_args(ap)
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -61,43 +58,14 @@ def main(argv=None):
         disp, flow = up(disp_h), up(flow_h)
         ws = torch.empty(lib.fn('dis_pose_workspace')(n, a.tl, a.h, a.w), dtype=torch.uint8, device='cuda')
         call = lambda: ops.track_poses(disp, flow, st.K, st.baseline, iters=a.iters, workspace=ws)
-        for _ in range(a.warmup):
-            r = call()
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.calls):
-                r = call()
-            e1.record()
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.calls)
-        med = statistics.median(ms)
-        side = torch.cuda.Stream()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            rg = call()
-        gms = []
-        for k in range(a.repeats + 1):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.calls):
-                graph.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            if k:                                  # the first window is the warm-up
-                gms.append(e0.elapsed_time(e1) / a.calls)
+        ms, gms, r, rg = time_call(call, a.warmup, a.repeats, a.calls)
         gmed = statistics.median(gms)
         same = all(bool(torch.equal(rg[k].view(torch.int32), r[k].view(torch.int32))) for k in r)
         model = byte_model(n, a.tl, a.h, a.w, a.iters, int(ws.numel()))
         total = sum(model.values())
         truth = pose_inputs.pair_truth(batch['R'], batch['t'])
         res = {'h': a.h, 'w': a.w, 'n': n, 'tl': a.tl, 'iters': a.iters, 'launches': 2 * (a.iters + 1),
-               'call_ms_median': round(med, 4), 'call_ms_min': round(min(ms), 4), 'call_ms_max': round(max(ms), 4),
-               'tracks_per_s': round(n / med * 1e3, 1), 'graph_ms_median': round(gmed, 4), 'graph_ms_min': round(min(gms), 4),
-               'graph_ms_max': round(max(gms), 4), 'graph_tracks_per_s': round(n / gmed * 1e3, 1), 'graph_equals_eager': same,
+               **timing_fields(n, ms, gms), 'graph_equals_eager': same,
                'us_per_launch': round(gmed * 1e3 / (2 * (a.iters + 1)), 2), 'pairs': n * a.tl * (a.tl - 1),
                'pairs_ok': int((r['stats'][..., 3] == 1).sum().item()) - n * a.tl,
                'max_R_error': float(np.abs(r['R_pair'].cpu().numpy() - truth[0]).max()),
@@ -113,9 +81,7 @@ def main(argv=None):
             res['max_R_distance_to_numpy'] = float(np.abs(ref['R_pair'] - r['R_pair'].cpu().numpy()).max())
         print(json.dumps(res))
         lines.append(res)
-    if a.json:
-        with open(a.json, 'w') as fp:
-            json.dump(lines, fp, indent=1)
+    emit(lines, a.json)
 
 
 if __name__ == '__main__':

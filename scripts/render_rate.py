@@ -9,6 +9,7 @@ hidden    the same triangle count with every object moved 4 m sideways, out of t
 host      synth.make_batch(bs = 1) at the same size in --host-procs processes (the generator the renderer stands next to)
 """
 import argparse
+import itertools
 import json
 import multiprocessing as mp
 import os
@@ -18,6 +19,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import rate_common as RC   # noqa: E402
 
 
 def dense_scene(hidden=False):
@@ -82,15 +85,8 @@ def main():
         for s in dscenes:
             run(s)
         torch.cuda.synchronize()
-        rates = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for k in range(a.calls):
-                run(dscenes[k % len(dscenes)])
-            e1.record()
-            torch.cuda.synchronize()
-            rates.append(a.calls / (e0.elapsed_time(e1) * 1e-3))
+        turn = itertools.cycle(dscenes)
+        rates = [1e3 / ms for ms in RC.windows(lambda: run(next(turn)), a.repeats, a.calls)[0]]
         return {'tracks_per_s': sorted(rates), 'median': float(np.median(rates)), 'faces': [len(s[1]) for s in scenes]}
 
     result['sampled'] = rate([render.sample_track(i, a.tl, 0, objs) for i in range(a.scenes)])

@@ -21,6 +21,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import rate_common as RC   # noqa: E402
+
 
 def byte_model(n, h, w, d):
     """-> dict launch family -> bytes of one call"""
@@ -37,10 +39,7 @@ def main(argv=None):
     ap.add_argument('--w', type=int, default=432)
     ap.add_argument('--n', type=int, default=4)
     ap.add_argument('--ndisp', type=int, nargs='+', default=[64, 128])
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=15)
-    ap.add_argument('--calls', type=int, default=10)
-    ap.add_argument('--json', default=None, help='also write the result lines to this file')
+    RC.add_timing_args(ap, warmup=5, repeats=15, calls=10)
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -55,32 +54,18 @@ def main(argv=None):
     lines = []
     for d in a.ndisp:
         ws = torch.empty(lib.fn('dis_sgm_workspace')(a.n, a.h, a.w, d), dtype=torch.uint8, device='cuda')
-        for _ in range(a.warmup):
-            disp = ops.sgm_disparity(im, pat, ndisp=d, workspace=ws)
-        torch.cuda.synchronize()
-        ms = []
-        for _ in range(a.repeats):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.calls):
-                disp = ops.sgm_disparity(im, pat, ndisp=d, workspace=ws)
-            e1.record()
-            torch.cuda.synchronize()
-            ms.append(e0.elapsed_time(e1) / a.calls)
+        ms, disp = RC.eager(lambda: ops.sgm_disparity(im, pat, ndisp=d, workspace=ws), a.warmup, a.repeats, a.calls)
         med = statistics.median(ms)
         model = byte_model(a.n, a.h, a.w, d)
         total = sum(model.values())
         valid = disp != 0
-        res = {'h': a.h, 'w': a.w, 'n': a.n, 'ndisp': d, 'call_ms_median': round(med, 4), 'call_ms_min': round(min(ms), 4),
-               'call_ms_max': round(max(ms), 4), 'frames_per_s': round(a.n / med * 1e3, 1), 'model_bytes': total,
+        res = {'h': a.h, 'w': a.w, 'n': a.n, 'ndisp': d, **RC.ms_fields('call_ms', ms), 'frames_per_s': round(a.n / med * 1e3, 1), 'model_bytes': total,
                'model_bytes_by_family': model, 'achieved_GB_per_s': round(total / med / 1e6, 1),
                'workspace_bytes': int(ws.numel()), 'valid_fraction': round(float(valid.float().mean()), 4),
                'valid_off_by_more_than_1px': round(float(((disp - truth).abs() > 1)[valid].float().mean()), 4)}
         print(json.dumps(res))
         lines.append(res)
-    if a.json:
-        with open(a.json, 'w') as fp:
-            json.dump(lines, fp, indent=1)
+    RC.emit(lines, a.json)
 
 
 if __name__ == '__main__':

@@ -23,11 +23,12 @@ rows of the stencil are read once per block from memory and again from LDS):
 import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+import rate_common as RC   # noqa: E402
 
 
 def byte_model(tl, h, w, grid, vertices, quads, value=True):
@@ -45,10 +46,7 @@ def main(argv=None):
     ap.add_argument('--tl', type=int, default=4)
     ap.add_argument('--res', type=int, default=256)
     ap.add_argument('--trunc', type=float, default=3.0)
-    ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--repeats', type=int, default=9)
-    ap.add_argument('--calls', type=int, default=20)
-    ap.add_argument('--json', default=None, help='also write the result to this file')
+    RC.add_timing_args(ap, calls=20)
     a = ap.parse_args(argv)
     import numpy as np
     import torch
@@ -71,32 +69,7 @@ def main(argv=None):
     mesh = lambda v=vol: ops.tsdf_mesh(v[0], v[1], v[2], origin, voxel, vcap=nv, fcap=nf, workspace=ws)
     both = lambda: mesh(integrate())
 
-    def windows(fn, skip_first=False):
-        ms = []
-        for k in range(a.repeats + (1 if skip_first else 0)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.calls):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            if k or not skip_first:
-                ms.append(e0.elapsed_time(e1) / a.calls)
-        return {'ms_median': round(statistics.median(ms), 4), 'ms_min': round(min(ms), 4), 'ms_max': round(max(ms), 4)}
-
-    def eager(fn):
-        for _ in range(a.warmup):
-            fn()
-        torch.cuda.synchronize()
-        return windows(fn)
-
-    def replayed(fn):
-        side = torch.cuda.Stream()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=side):
-            out = fn()
-        return windows(graph.replay, skip_first=True), out
+    eager = lambda fn: RC.ms_fields('ms', RC.eager(fn, a.warmup, a.repeats, a.calls)[0])
 
     res = {'h': a.h, 'w': a.w, 'tl': a.tl, 'res': a.res, 'grid': list(grid), 'lattice_points': nx * ny * nz, 'voxel': voxel, 'trunc': trunc,
            'vertices': nv, 'triangles': nf, 'observed': round(float((vol[1] > 0).float().mean().item()), 4),
@@ -106,7 +79,8 @@ def main(argv=None):
     groups = {'integrate': model['integrate'], 'mesh': sum(v for k, v in model.items() if k != 'integrate'), 'both': sum(model.values())}
     for name, fn in (('integrate', integrate), ('mesh', mesh), ('both', both)):
         e = eager(fn)
-        g, out = replayed(fn)
+        gms, out = RC.replayed(fn, a.repeats, a.calls)
+        g = RC.ms_fields('ms', gms)
         res[name] = {'call': e, 'tracks_per_s': round(1e3 / e['ms_median'], 1), 'graph': g, 'graph_tracks_per_s': round(1e3 / g['ms_median'], 1),
                      'model_bytes': groups[name], 'model_GB_per_s': round(groups[name] / g['ms_median'] / 1e6, 1)}
         if name == 'both':
@@ -123,9 +97,7 @@ def main(argv=None):
     for name in ('integrate', 'mesh', 'both'):
         res[name]['share_of_copy_rate'] = round(res[name]['model_GB_per_s'] / copy_rate, 4)
     print(json.dumps(res))
-    if a.json:
-        with open(a.json, 'w') as fp:
-            json.dump(res, fp, indent=1)
+    RC.emit(res, a.json)
 
 
 if __name__ == '__main__':
