@@ -11,7 +11,7 @@ to frames.npz through a temporary file; its other arrays stay byte-identical and
 whose pairs failed is listed as failed and left as it is.
 
     python -m depthinspace_amd.data.presave_pose ROOT [--disp gt|sgm|single_frame|multi_frame] [--iters N] [--scale S] [--damping D]
-                                                      [--min-corr N] [--force] [--report] [--pack]
+                                                      [--min-corr N] [--force] [--report] [--pack] [--joint] [--joint-iters N]
 
 A track that already stores R and t is skipped unless --force is given: rendered tracks keep their exact poses.  --report also
 estimates the tracks that are skipped and prints one line over the dataset: the pairs that are ok / failed, the mean share of the
@@ -20,8 +20,16 @@ pixels a pair uses, its mean weight and weighted rms residual in pixels, and the
 Where a track stored poses before the run, the rotation angle and the translation error (over the median depth) of the estimated
 relative poses against the stored ones are added.
 
-This is pairwise and nothing more: no bundle adjustment over the track, no loop closure, no estimation of the intrinsics; the pairs
-are independent, and only the pairs with frame 0 set the stored poses.
+Without --joint this is pairwise and nothing more: the pairs are independent, and only the pairs with frame 0 set the stored poses.
+--joint adds a second stage, ops.refine_track_poses (dis_refine_track_poses): one pose per frame, frame 0 fixed, --joint-iters
+Gauss-Newton steps on the residuals of all ordered pairs that the pairwise stage reports as ok at once - the same per-pixel terms, one
+6 (tl - 1) system per track - so that one bad pair with frame 0 is corrected by the pairs among the other frames, and the frames 1 ..
+tl - 1 are fitted to each other.  It starts from the pairwise result; a frame both of whose pairs with frame 0 failed is reached
+through the other ok pairs (chain_track), and such a track is no longer listed as failed.  A track whose joint system is singular is
+written with its composed pairwise poses and counted (`joint_failed`); --report adds the joint rms residual over the contributing
+pairs, their share of the ordered pairs, and against stored poses the errors of the joint poses (`joint_gt_rot`, `joint_gt_trans`,
+over all ordered pairs) next to the pairwise ones.  Still not done: the intrinsics are taken as given, there is no loop closure
+across tracks, no step control beyond the damping term, and a track has at most four frames.
 """
 import argparse
 import os
@@ -72,6 +80,33 @@ def compose_track(R_pair, t_pair, ok):
             R[j], t[j] = Rj0.T, -Rj0.T @ np.asarray(t_pair[j, 0], dtype=np.float64)
         else:
             return None
+    return R.astype(np.float32), t.astype(np.float32)
+
+
+def chain_track(R_pair, t_pair, ok):
+    """compose_track for the start of the joint refinement: a frame both of whose pairs with frame 0 failed is reached through the ok
+    pairs instead.  A breadth-first walk from frame 0: the frames reached are visited in the order they were reached, and each one
+    gives its pose to the frames not reached yet, in index order, through the pair (a, b) or the inverse of the pair (b, a) where
+    that one failed.  A frame next to frame 0 gets the values of compose_track.  None if a frame cannot be reached at all."""
+    tl = R_pair.shape[0]
+    R, t = np.zeros((tl, 3, 3), np.float64), np.zeros((tl, 3), np.float64)
+    R[0] = np.eye(3)
+    reached, queue = {0}, [0]
+    while queue:
+        a = queue.pop(0)
+        for b in range(tl):
+            if b in reached or not (ok[a, b] or ok[b, a]):
+                continue
+            if ok[a, b]:
+                Rab, tab = np.asarray(R_pair[a, b], dtype=np.float64), np.asarray(t_pair[a, b], dtype=np.float64)
+            else:
+                Rba = np.asarray(R_pair[b, a], dtype=np.float64)
+                Rab, tab = Rba.T, -Rba.T @ np.asarray(t_pair[b, a], dtype=np.float64)
+            R[b], t[b] = Rab @ R[a], Rab @ t[a] + tab
+            reached.add(b)
+            queue.append(b)
+    if len(reached) < tl:
+        return None
     return R.astype(np.float32), t.astype(np.float32)
 
 
@@ -146,12 +181,53 @@ def estimate_pairs(disps, flows, settings, iters=6, scale=1.0, damping=0.0, min_
     return tuple(r[k].cpu().numpy() for k in ('R_pair', 't_pair', 'stats'))
 
 
+def refine_tracks(disps, flows, settings, R_init, t_init, use, iters=6, scale=1.0, damping=0.0, min_corr=64, device='cuda'):
+    """the lists of estimate_pairs with R_init (n, tl, 3, 3), t_init (n, tl, 3) float32 and use (n, tl, tl) bool -> R (n, tl, 3, 3), t (n, tl, 3),
+    pair_stats (n, tl, tl, 4), track_stats (n, 4) float32 numpy (one call of ops.refine_track_poses)"""
+    from .. import ops
+    dev = torch.device(device)
+    up = lambda a, dt=np.float32: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    r = ops.refine_track_poses(up(np.stack(disps)), up(np.stack(flows)), np.asarray(settings.K, dtype=np.float32), settings.baseline,
+                               up(R_init), up(t_init), up(use, np.uint8), iters=iters, scale=scale, damping=damping, min_corr=min_corr)
+    return tuple(r[k].cpu().numpy() for k in ('R', 't', 'pair_stats', 'track_stats'))
+
+
+def joint_terms(R, t, track_stats, depth, stored=None):
+    """the sums one jointly refined track adds to the report.  R (tl, 3, 3), t (tl, 3), track_stats (4) of ops.refine_track_poses -> dict:
+    joint_tracks (1), joint_failed (status 0: nothing else is added), joint_resid (the rms residual over the contributing pairs),
+    joint_share (their share of the ordered pairs); with stored poses joint_gt_pairs (all ordered pairs), joint_gt_rot, joint_gt_trans"""
+    tl = len(R)
+    if track_stats[3] == 0:
+        return {'joint_tracks': 1, 'joint_failed': 1}
+    r = {'joint_tracks': 1, 'joint_failed': 0, 'joint_resid': float(track_stats[2]), 'joint_share': float(track_stats[0]) / (tl * (tl - 1))}
+    if stored is not None:
+        off = ~np.eye(tl, dtype=bool)
+        (Rj, tj), (Rs, ts) = relative_poses(R, t), relative_poses(*stored)
+        r['joint_gt_pairs'] = int(off.sum())
+        r['joint_gt_rot'] = float(rotation_angle(Rj[off] @ np.swapaxes(Rs[off], -1, -2)).sum())
+        r['joint_gt_trans'] = float((np.linalg.norm(tj[off] - ts[off], axis=-1) / depth).sum())
+    return r
+
+
+def joint_line(acc):
+    """the sums of joint_terms added over the tracks -> what the joint stage adds to the dict that is printed"""
+    div = lambda a, b: a / b if b else float('nan')
+    good = acc['joint_tracks'] - acc['joint_failed']
+    res = {'joint_resid': div(acc.get('joint_resid', 0.0), good), 'joint_share': div(acc.get('joint_share', 0.0), good)}
+    if acc.get('joint_gt_pairs'):
+        res['joint_gt_rot'] = acc['joint_gt_rot'] / acc['joint_gt_pairs']
+        res['joint_gt_trans'] = acc['joint_gt_trans'] / acc['joint_gt_pairs']
+    return res
+
+
 def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_corr=64, force=False, report=False, pack=False,
-                 device='cuda'):
+                 device='cuda', joint=False, joint_iters=6):
     """Adds R (tl, 3, 3) and t (tl, 3) to the frames.npz of every track directory of data_root that has none (force: of all of them),
     each through a temporary file; the other arrays stay byte-identical.  pack: re-runs packed.pack_dataset.  Returns the number of
     tracks written, or with report=True - which also estimates the tracks it does not write - the dict of report_line with `tracks`,
-    `written` and `failed_tracks` added (printed as one line).  The tracks that failed are printed by name."""
+    `written` and `failed_tracks` added (printed as one line).  The tracks that failed are printed by name.  joint: the pairwise result
+    is refined by ops.refine_track_poses (joint_iters steps) before it is written - see the module's docstring; the report then also
+    carries the keys of joint_line and `joint_failed`, the tracks written with their pairwise poses."""
     data_root = str(data_root)
     settings = load_settings(data_root)
     K = np.asarray(settings.K, dtype=np.float64)
@@ -162,7 +238,7 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
         write = force or stored is None
         if write or report:
             todo.append((d, write, stored))
-    done, failed, acc, k = 0, [], {}, 0
+    done, failed, joint_failed, acc, k = 0, [], [], {}, 0
     while k < len(todo):
         disps, flows = [], []
         while k < len(todo) and len(disps) < BATCH:       # up to four tracks of one length per call
@@ -173,30 +249,56 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
             flows.append(load_flow(todo[k][0], disp.shape[0]))
             k += 1
         Rp, tp, st = estimate_pairs(disps, flows, settings, iters, scale, damping, min_corr, device)
+        ok = st[..., 3] != 0
+        if joint:
+            # the start: the pairwise result chained from frame 0; a track that no chain covers takes no part (no pair is used: it fails)
+            starts = [chain_track(Rp[b], tp[b], ok[b]) for b in range(len(disps))]
+            tl = disps[0].shape[0]
+            R0 = np.stack([np.broadcast_to(np.eye(3, dtype=np.float32), (tl, 3, 3)) if s_ is None else s_[0] for s_ in starts])
+            t0 = np.stack([np.zeros((tl, 3), np.float32) if s_ is None else s_[1] for s_ in starts])
+            use = np.stack([ok[b] & (starts[b] is not None) for b in range(len(disps))])
+            Rj, tj, _, jst = refine_tracks(disps, flows, settings, R0, t0, use, joint_iters, scale, damping, min_corr, device)
         for b, (d, write, stored) in enumerate(todo[k - len(disps):k]):
             if report:
-                terms = report_terms(Rp[b], tp[b], st[b], disps[b].shape[-2] * disps[b].shape[-1], median_depth(disps[b], fb), stored)
+                depth = median_depth(disps[b], fb)
+                terms = report_terms(Rp[b], tp[b], st[b], disps[b].shape[-2] * disps[b].shape[-1], depth, stored)
+                if joint and starts[b] is not None:
+                    terms.update(joint_terms(Rj[b], tj[b], jst[b], depth, stored))
                 for key, v in terms.items():
                     acc[key] = acc.get(key, 0) + v
             if not write:
                 continue
-            poses = compose_track(Rp[b], tp[b], st[b][..., 3] != 0)
+            if joint:
+                poses = starts[b]
+                if poses is not None and jst[b, 3] != 0:
+                    poses = (Rj[b], tj[b])
+                elif poses is not None:
+                    joint_failed.append(d)
+            else:
+                poses = compose_track(Rp[b], tp[b], ok[b])
             if poses is None:
                 failed.append(d)
                 continue
             rewrite_npz(os.path.join(d, 'frames.npz'), {'R': poses[0], 't': poses[1]})
             done += 1
     if failed:
-        print(f'{len(failed)} tracks failed (a frame without an estimated pair with frame 0) and were left as they are: '
-              + ', '.join(os.path.basename(d) for d in failed))
+        why = 'a frame that no chain of estimated pairs reaches from frame 0' if joint else 'a frame without an estimated pair with frame 0'
+        print(f'{len(failed)} tracks failed ({why}) and were left as they are: ' + ', '.join(os.path.basename(d) for d in failed))
+    if joint_failed:
+        print(f'{len(joint_failed)} tracks were written with their pairwise poses (the joint system was singular): '
+              + ', '.join(os.path.basename(d) for d in joint_failed))
     if pack:
         packed.pack_dataset(data_root)
     if not report:
         return done
     res = report_line(acc) if acc else {}
+    if acc.get('joint_tracks'):
+        res.update(joint_line(acc))
     res.update(tracks=len(todo), written=done, failed_tracks=len(failed))
-    print(f'poses from the {source} disparities over {data_root} (iters {iters}, scale {scale:g}, damping {damping:g}): '
-          + report_text(res, '.6g'))
+    if joint:
+        res.update(joint_failed=len(joint_failed))
+    print(f'poses from the {source} disparities over {data_root} (iters {iters}, scale {scale:g}, damping {damping:g}'
+          + (f', joint iters {joint_iters}' if joint else '') + '): ' + report_text(res, '.6g'))
     return res
 
 
@@ -212,8 +314,11 @@ def main(argv=None):
     ap.add_argument('--force', action='store_true', help='also rewrite the poses that are stored')
     ap.add_argument('--report', action='store_true', help='also print the quality figures over the dataset')
     ap.add_argument('--pack', action='store_true', help='also (re)write the packed files (data/packed.py)')
+    ap.add_argument('--joint', action='store_true', help='refine the poses of a track jointly over all its ok pairs before they are written')
+    ap.add_argument('--joint-iters', type=int, default=6, help='Gauss-Newton steps of the joint refinement (1 .. 64)')
     a = ap.parse_args(argv)
-    r = presave_pose(a.root, a.disp, a.iters, a.scale, a.damping, a.min_corr, force=a.force, report=a.report, pack=a.pack)
+    r = presave_pose(a.root, a.disp, a.iters, a.scale, a.damping, a.min_corr, force=a.force, report=a.report, pack=a.pack, joint=a.joint,
+                     joint_iters=a.joint_iters)
     print(f'{r["written"] if a.report else r} tracks written under {a.root}')
 
 

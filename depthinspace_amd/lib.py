@@ -171,6 +171,8 @@ SIGS = {
     'dis_fuse_track': 'pppp' + 'f' + 'p' + 'f' + 'ii' + 'p' + 'iiii' + 'pl' + 'p',
     'dis_pose_workspace': 'iiii',
     'dis_track_poses': 'ppp' + 'f' + 'i' + 'ff' + 'i' + 'ppp' + 'iiii' + 'pl' + 'p',
+    'dis_pose_joint_workspace': 'iiii',
+    'dis_refine_track_poses': 'ppp' + 'f' + 'ppp' + 'i' + 'ff' + 'i' + 'pppp' + 'iiii' + 'pl' + 'p',
     'dis_tsdf_integrate': 'pppp' + 'f' + 'pp' + 'ff' + 'ppp' + 'iiiiii' + 'p',
     'dis_tsdf_mesh_workspace': 'iii',
     'dis_tsdf_mesh': 'pppp' + 'f' + 'iii' + 'p' + 'iii' + 'pl' + 'p',
@@ -183,6 +185,7 @@ _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_wor
              'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace', 'dis_geo_loss_bwd_det_workspace',
              'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace',
+             'dis_pose_joint_workspace',
              'dis_tsdf_mesh_workspace'}
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}

@@ -2934,6 +2934,49 @@ def track_poses(disp, flow, K, baseline, iters=6, scale=1.0, damping=0.0, min_co
     return res
 
 
+def refine_track_poses(disp, flow, K, baseline, R_init, t_init, pair_use=None, iters=6, scale=1.0, damping=0.0, min_corr=64,
+                       workspace=None):
+    """dis_refine_track_poses: disp, flow, K and baseline as in track_poses, with one world pose per frame to start from, R_init
+    (n, tl, 3, 3), t_init (n, tl, 3) (X_c = R X_w + t) -> the poses refined jointly on the residuals of every used ordered pair, frame 0
+    kept where it is (include/dis_hip.h, section "track poses"; tests/pose_joint_ref.py restates it in numpy).  pair_use: an optional
+    (n, tl, tl) uint8 (or bool) device tensor, non-zero where the pair (i, j) is used - the status of track_poses, say; None: every
+    pair.  `iters` (1 .. 64) Gauss-Newton steps on the 6 (tl - 1) system, every pass weighted by 1 / (1 + r^2 / scale^2)^2; damping >= 0
+    adds damping * diag(A); a pair with fewer than min_corr (>= 6) usable pixels does not contribute to a pass; a track whose system is
+    singular - a frame that no contributing pair touches - fails and keeps its last good state.
+    -> a dict of device tensors: R (n, tl, 3, 3), t (n, tl, 3), pair_stats (n, tl, tl, 4) fp32 = {pixels used, mean weight, weighted rms
+    residual in pixels, contributed} of the closing pass, track_stats (n, 4) = {contributing pairs, their pixels, their weighted rms
+    residual, status (1 ok, 0 failed)}.  The inputs are data: no autograd.  2 (iters + 1) launches on the current stream, no
+    synchronisation; workspace: an optional uint8 tensor of at least dis_pose_joint_workspace(...) bytes to reuse between calls (and
+    what makes the call capturable without an allocation besides the outputs)."""
+    _chk(disp, flow, R_init, t_init)
+    n, tl, h, w = _track_dims('refine_track_poses', disp)
+    if tuple(flow.shape) != (n, tl * tl, 2, h, w):
+        raise RuntimeError('refine_track_poses: flow (n, tl * tl, 2, H, W) is expected')
+    if tuple(R_init.shape) != (n, tl, 3, 3) or tuple(t_init.shape) != (n, tl, 3):
+        raise RuntimeError('refine_track_poses: R_init (n, tl, 3, 3) and t_init (n, tl, 3) are expected')
+    if pair_use is not None:
+        if not (isinstance(pair_use, torch.Tensor) and pair_use.is_cuda and pair_use.dtype in (torch.uint8, torch.bool)
+                and pair_use.is_contiguous() and tuple(pair_use.shape) == (n, tl, tl)):
+            raise RuntimeError('refine_track_poses: pair_use must be a contiguous (n, tl, tl) uint8 or bool CUDA(HIP) tensor')
+    need = lib.fn('dis_pose_joint_workspace')(n, tl, h, w)
+    if need < 0:
+        raise lib.DisHipError(f'dis_pose_joint_workspace: unsupported extents n={n} tl={tl} h={h} w={w}')
+    iters, scale, damping, min_corr, baseline = int(iters), float(scale), float(damping), int(min_corr), float(baseline)
+    K4 = _k4(K)
+    if not (1 <= iters <= 64 and _fin(scale) and scale > 0 and _fin(damping) and damping >= 0 and min_corr >= 6 and all(_fin(v) for v in K4)
+            and K4[0] > 0 and K4[1] > 0 and _fin(baseline) and baseline > 0):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'refine_track_poses: unsupported configuration iters={iters} scale={scale} damping={damping} '
+                              f'min_corr={min_corr} K={K4} baseline={baseline}')
+    dev = disp.device
+    workspace = _workspace('refine_track_poses', need, workspace, dev)
+    res = {'R': torch.empty((n, tl, 3, 3), dtype=torch.float32, device=dev), 't': torch.empty((n, tl, 3), dtype=torch.float32, device=dev),
+           'pair_stats': torch.empty((n, tl, tl, 4), dtype=torch.float32, device=dev),
+           'track_stats': torch.empty((n, 4), dtype=torch.float32, device=dev)}
+    lib.call('dis_refine_track_poses', disp, flow, lib.host_floats(K4), baseline, R_init, t_init, pair_use, iters, scale, damping, min_corr,
+             res['R'], res['t'], res['pair_stats'], res['track_stats'], n, tl, h, w, workspace, int(workspace.numel()))
+    return res
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # volumetric fusion (csrc/tsdf.hip; data/mesh.py writes the meshes)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -987,6 +987,52 @@ int dis_track_poses(const float* disp, const float* flow, const float* K4_host, 
                     int min_corr, float* R_pair, float* t_pair, float* stats, int n, int tl, int h, int w, void* workspace,
                     long workspace_bytes, void* stream);
 
+/* dis_refine_track_poses: the second stage.  One pose per frame of a track, frame 0 fixed, refined at once on the residuals of every used
+ * ordered pair - the per-pixel expressions of dis_track_poses above, unchanged: valid, target, matched, used, residual, Jacobian and the
+ * 30 sums - so that the pairs that dis_track_poses estimates independently hold each other.  tests/pose_joint_ref.py restates what is
+ * added here in numpy, operand order included.
+ *   state      (R_k, t_k) per frame in fp64, X_c = R_k X_w + t_k, converted from R_init, t_init by the call itself.  Frame 0 is never
+ *              moved: its output equals its input bit for bit.
+ *   pair       pass k = 0 .. iters forms, for every used pair (i, j), in fp64
+ *                R_ij[r][c] = (R_j[r][0] R_i[c][0] + R_j[r][1] R_i[c][1]) + R_j[r][2] R_i[c][2],
+ *                t_ij[r] = t_j[r] - ((R_ij[r][0] t_i[0] + R_ij[r][1] t_i[1]) + R_ij[r][2] t_i[2]);
+ *              their fp32 rounding is the state of the per-pixel expressions.  Every pass, the first included, uses the weight g g (the
+ *              refinement starts from an estimate: there is no unweighted pass).  pair_use[b][i][j] != 0: the pair is used; NULL:
+ *              every pair off the diagonal; the diagonal is ignored.  The flows of a pair that is not used are not read.
+ *   contribute a pair contributes to a pass iff it is used and its n >= min_corr in that pass.
+ *   assembly   fp64.  With Ad_ij = [[R_ij, 0], [[t_ij]x R_ij, R_ij]] acting on (omega, nu) - ([t]x R)[r][c] = t[r+1] R[r+2][c] -
+ *              t[r+2] R[r+1][c], indices mod 3, from the fp64 R_ij, t_ij - a left perturbation xi_k of every frame perturbs the pair by
+ *              xi_j - Ad_ij xi_i.  Per pair M = H Ad, N = Ad^T M, q = Ad^T g, every element the sum over k = 0 .. 5 in this order from the
+ *              first product (the structural zeros of Ad are multiplied); then, over the contributing pairs in ascending (i, j), from
+ *              zero: A[j,j] += H, A[i,i] += N, A[j,i] -= M, A[i,j] -= M^T, b[j] += g, b[i] -= q.  The rows and columns of frame 0 are
+ *              dropped: the order is 6 (tl - 1).
+ *   solve      Cholesky of A + damping diag(A), column by column as for a pair; L y = -b with k ascending, L^T delta = y with k
+ *              descending, an unknown being its row's sum times 1 / L_kk (formed once per column); frame k >= 1 takes delta[6 (k - 1) .. 6 k) = (omega, nu) through the update of dis_track_poses (dR from omega,
+ *              R_k <- dR R_k, t_k <- dR t_k + nu).
+ *   failure    a track fails when a pivot is not > 0 or not finite - which a frame that no contributing pair touches gives, and so does a
+ *              pass without any contributing pair.  A failed track keeps the state of its last good step (the init if there is none)
+ *              and takes no further steps.
+ *   closing    after the last step one more pass at the final state yields the statistics.
+ * disp, flow, K4_host, baseline: as in dis_track_poses.  R_init (n, tl, 3, 3), t_init (n, tl, 3) fp32, pair_use (n, tl, tl) uint8 or NULL:
+ * DEVICE.  Outputs, DEVICE, every element written, fp32: R (n, tl, 3, 3), t (n, tl, 3); pair_stats (n, tl, tl, 4) = {n, S_w / n,
+ * sqrt(S_c / S_w), contributed} of the closing pass, zeros for a pair that is not used, {0, 0, 0, 1} on the diagonal; track_stats (n, 4) =
+ * {contributing pairs, sum n, sqrt(sum S_c / sum S_w), status}, the sums over the contributing pairs of the closing pass in ascending
+ * (i, j); status 1: every step was taken, 0: failed.  A ratio is 0 where a denominator is 0.
+ * iters + 1 accumulate launches (the grid and the reduction of dis_track_poses; the pair's state is composed inside the kernel) and
+ * iters + 1 solve launches (a workgroup per track: the records of a pair added in ascending workgroup order, the system assembled,
+ * factored and solved in LDS): 2 (iters + 1) launches.  The hand-off between them is the launch boundary alone: no atomics, no flags
+ * polled between workgroups, so two calls give the same bits.  No allocation, no synchronisation: capturable.
+ * workspace: dis_pose_joint_workspace(n, tl, h, w) BYTES (-1: unsupported extents), 16-byte aligned, no initialisation.
+ * Checks, in this order, all before any launch: a NULL pointer other than pair_use -> DIS_ERR_NULL; n < 1, tl outside 2 .. 4, h or w
+ * outside 2 .. 8192, n tl tl 2 h w >= 2^31 -> DIS_ERR_BAD_SHAPE; iters outside 1 .. 64, scale not positive and finite, damping negative or
+ * not finite, min_corr < 6, fx, fy or baseline not positive and finite, cx or cy not finite, workspace_bytes below
+ * dis_pose_joint_workspace(...), a misaligned workspace -> DIS_ERR_UNSUPPORTED. */
+long dis_pose_joint_workspace(int n, int tl, int h, int w);
+int dis_refine_track_poses(const float* disp, const float* flow, const float* K4_host, float baseline, const float* R_init,
+                           const float* t_init, const unsigned char* pair_use, int iters, float scale, float damping, int min_corr,
+                           float* R, float* t, float* pair_stats, float* track_stats, int n, int tl, int h, int w, void* workspace,
+                           long workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- volumetric fusion --------- */
 
 /* The per-frame disparity maps of ONE track -> a truncated signed distance volume on a regular lattice, and the volume -> an indexed

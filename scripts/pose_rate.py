@@ -12,7 +12,13 @@ there is no per-pixel workspace): every pass of every pair reads its frame's dis
 the four gathered disparities of the other frame are expected to hit in the caches.  The partial sums (256 B per workgroup and pass)
 and the state are counted too; they are small.
 
+The joint leg (a second result line per batch size, `leg: joint`) times ops.refine_track_poses in the same session, in the same windows, at
+the same number of steps, started from the composed result of the pairwise call just measured, with its status as pair_use.  A joint
+pass does the per-pixel work of a pairwise one, so the byte model is the same; `joint_over_pairwise` is the ratio of the two replay
+times.  --no-joint leaves the leg out.
+
     python scripts/pose_rate.py [--h 512 --w 432 --tl 4 --iters 6] [--batches 1 4] [--warmup 3] [--repeats 9] [--calls 50] [--json PATH]
+                                [--no-joint]
 """
 import argparse
 import json
@@ -40,6 +46,7 @@ def main(argv=None):
     ap.add_argument('--tl', type=int, default=4)
     ap.add_argument('--iters', type=int, default=6)
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 4], help='tracks per call')
+    ap.add_argument('--no-joint', action='store_true', help='leave out the leg of ops.refine_track_poses')
     add_timing_args(ap)
     a = ap.parse_args(argv)
     import numpy as np
@@ -81,6 +88,28 @@ def main(argv=None):
             res['max_R_distance_to_numpy'] = float(np.abs(ref['R_pair'] - r['R_pair'].cpu().numpy()).max())
         print(json.dumps(res))
         lines.append(res)
+        if a.no_joint:
+            continue
+        from depthinspace_amd.data.presave_pose import compose_track
+        Rp, tp, stat = (r[k].cpu().numpy() for k in ('R_pair', 't_pair', 'stats'))
+        starts = [compose_track(Rp[b], tp[b], stat[b, ..., 3] != 0) for b in range(n)]
+        R0, t0 = up(np.stack([s_[0] for s_ in starts])), up(np.stack([s_[1] for s_ in starts]))
+        use = (r['stats'][..., 3] != 0).to(torch.uint8).contiguous()
+        wsj = torch.empty(lib.fn('dis_pose_joint_workspace')(n, a.tl, a.h, a.w), dtype=torch.uint8, device='cuda')
+        jcall = lambda: ops.refine_track_poses(disp, flow, st.K, st.baseline, R0, t0, use, iters=a.iters, workspace=wsj)
+        jms, jgms, j, jg = time_call(jcall, a.warmup, a.repeats, a.calls)
+        jmed = statistics.median(jgms)
+        jR, jt = pose_inputs.pair_truth(j['R'].cpu().numpy(), j['t'].cpu().numpy())
+        world = pose_inputs.pair_truth(batch['R'], batch['t'])
+        jres = {'leg': 'joint', 'h': a.h, 'w': a.w, 'n': n, 'tl': a.tl, 'iters': a.iters, 'launches': 2 * (a.iters + 1),
+                **timing_fields(n, jms, jgms), 'graph_equals_eager': all(bool(torch.equal(jg[k].view(torch.int32), j[k].view(torch.int32))) for k in j),
+                'us_per_launch': round(jmed * 1e3 / (2 * (a.iters + 1)), 2), 'joint_over_pairwise': round(jmed / gmed, 4),
+                'tracks_ok': int((j['track_stats'][:, 3] == 1).sum().item()),
+                'contributing_pairs': int(j['track_stats'][:, 0].sum().item()),
+                'max_R_error': float(np.abs(jR - world[0]).max()), 'max_t_error': float(np.abs(jt - world[1]).max()),
+                'model_bytes': total, 'achieved_GB_per_s': round(total / jmed / 1e6, 1), 'workspace_bytes': int(wsj.numel())}
+        print(json.dumps(jres))
+        lines.append(jres)
     emit(lines, a.json)
 
 
