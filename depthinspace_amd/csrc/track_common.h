@@ -1,4 +1,4 @@
-// Parts the track tools share (render.hip, sgm.hip, flow.hip, fuse.hip, pose.hip, tsdf.hip): the finite tests, the workspace carver,
+// Parts the track tools share (render.hip, sgm.hip, flow.hip, fuse.hip, pose.hip, tsdf.hip, raycast.hip): the finite tests, the workspace carver,
 // the pinhole camera, the rigid transforms and the scan / count / rank steps of a stream compaction.  Every helper is inlined, and a
 // device helper holds an expression only where the tools spell it token for token alike: the build uses -ffp-contract=off and the
 // restatements tests/*_ref.py fix the operand order.  The three projections into a frame are NOT shared, they differ:
@@ -42,6 +42,16 @@ static inline bool track_camera(const float* K4_host, float baseline, TrackCamer
   c->fb = c->fx * baseline;
   return track_pos_finite(c->fx) && track_pos_finite(c->fy) && track_pos_finite(baseline) && track_finite(c->cx) && track_finite(c->cy) &&
          track_pos_finite(c->fb);
+}
+
+// the lattice of a volume (tsdf.hip, raycast.hip): every extent in 2 .. 1024
+static inline bool tsdf_grid_ok(int nx, int ny, int nz) {
+  return nx >= 2 && ny >= 2 && nz >= 2 && nx <= 1024 && ny <= 1024 && nz <= 1024;
+}
+// false: not a lattice origin
+static inline bool tsdf_origin(const float* origin3_host, float* ox, float* oy, float* oz) {
+  *ox = origin3_host[0], *oy = origin3_host[1], *oz = origin3_host[2];
+  return track_finite(*ox) && track_finite(*oy) && track_finite(*oz);
 }
 
 // pixel (u, v) with disparity d -> its point in the camera's frame

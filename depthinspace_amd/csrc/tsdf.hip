@@ -289,15 +289,6 @@ __global__ __launch_bounds__(TSDF_BLOCK) void tsdf_face_kernel(const unsigned ch
   }
 }
 
-static inline bool tsdf_grid_ok(int nx, int ny, int nz) {
-  return nx >= 2 && ny >= 2 && nz >= 2 && nx <= 1024 && ny <= 1024 && nz <= 1024;
-}
-// false: not a lattice origin
-static inline bool tsdf_origin(const float* origin3_host, float* ox, float* oy, float* oz) {
-  *ox = origin3_host[0], *oy = origin3_host[1], *oz = origin3_host[2];
-  return track_finite(*ox) && track_finite(*oy) && track_finite(*oz);
-}
-
 extern "C" int dis_tsdf_integrate(const float* disp, const float* R, const float* t, const float* K4_host, float baseline, const float* value,
                                   const float* origin3_host, float voxel, float trunc, float* tsdf, unsigned char* weight, float* vvalue,
                                   int tl, int h, int w, int nx, int ny, int nz, void* stream) {

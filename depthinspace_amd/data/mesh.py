@@ -56,10 +56,10 @@ def place_volume(points, res=256, voxel=None, trunc_voxels=3.0):
     return origin, voxel, trunc, grid
 
 
-def mesh_arrays(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3.0, min_weight=1, tol=0.01, min_views=2, device='cuda'):
-    """one track, float32 numpy in, through ops.fuse_track (the placement), ops.tsdf_integrate and ops.tsdf_mesh -> dict of numpy arrays
-    xyz, normal (V, 3), value (V), views (V) uint8, faces (M, 3) int32, and origin, voxel, trunc, grid, observed (the share of lattice
-    points with weight > 0) - or None when fuse_track keeps no point"""
+def integrate_track(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3.0, tol=0.01, min_views=2, device='cuda'):
+    """one track, float32 numpy in: the volume placed around the points ops.fuse_track keeps (place_volume) and integrated by
+    ops.tsdf_integrate - what data/mesh.py and data/raycast.py share.  -> dict of the device tensors tsdf, weight, vvalue, R, t and
+    origin, voxel, trunc, grid, K - or None when fuse_track keeps no point or the box has no extent"""
     from .. import ops
     dev = torch.device(device)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
@@ -76,9 +76,21 @@ def mesh_arrays(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3
         return None
     origin, vx, trunc, grid = place
     tsdf, weight, vvalue = ops.tsdf_integrate(d_disp, d_R, d_t, K, settings.baseline, d_val, origin=origin, voxel=vx, trunc=trunc, grid=grid)
-    g = ops.tsdf_mesh(tsdf, weight, vvalue, origin, vx, min_weight=min_weight)
+    return dict(tsdf=tsdf, weight=weight, vvalue=vvalue, R=d_R, t=d_t, origin=origin, voxel=vx, trunc=trunc, grid=grid, K=K)
+
+
+def mesh_arrays(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3.0, min_weight=1, tol=0.01, min_views=2, device='cuda'):
+    """one track, float32 numpy in, through integrate_track (the placement by ops.fuse_track, ops.tsdf_integrate) and ops.tsdf_mesh ->
+    dict of numpy arrays xyz, normal (V, 3), value (V), views (V) uint8, faces (M, 3) int32, and origin, voxel, trunc, grid, observed
+    (the share of lattice points with weight > 0) - or None when fuse_track keeps no point"""
+    from .. import ops
+    v = integrate_track(disp, R, t, value, settings, res, voxel, trunc_voxels, tol, min_views, device)
+    if v is None:
+        return None
+    g = ops.tsdf_mesh(v['tsdf'], v['weight'], v['vvalue'], v['origin'], v['voxel'], min_weight=min_weight)
     out = {k: g[k].cpu().numpy() for k in ('xyz', 'normal', 'value', 'views', 'faces')}
-    out.update(origin=origin, voxel=vx, trunc=trunc, grid=grid, observed=float((weight > 0).float().mean().item()))
+    out.update(origin=v['origin'], voxel=v['voxel'], trunc=v['trunc'], grid=v['grid'],
+               observed=float((v['weight'] > 0).float().mean().item()))
     return out
 
 

@@ -2978,7 +2978,7 @@ def refine_track_poses(disp, flow, K, baseline, R_init, t_init, pair_use=None, i
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# volumetric fusion (csrc/tsdf.hip; data/mesh.py writes the meshes)
+# volumetric fusion (csrc/tsdf.hip, csrc/raycast.hip; data/mesh.py writes the meshes, data/raycast.py the per-frame maps)
 # ----------------------------------------------------------------------------------------------------------------------
 def tsdf_integrate(disp, R, t, K, baseline, value=None, *, origin, voxel, trunc, grid):
     """dis_tsdf_integrate: the disparity maps disp (tl, H, W) or (tl, 1, H, W) of ONE track, 1 <= tl <= 4, with the poses R (tl, 3, 3),
@@ -3068,3 +3068,46 @@ def tsdf_mesh(tsdf, weight, vvalue, origin, voxel, min_weight=1, vcap=None, fcap
         vcap = nv if vcap is None else int(vcap)
         fcap = nf if fcap is None else int(fcap)
     return run(int(vcap), int(fcap), want_dense)
+
+
+def tsdf_raycast(tsdf, weight, vvalue, origin, voxel, R, t, K, baseline, size, step=None, min_weight=1, workspace=None, variant=0):
+    """dis_tsdf_raycast: the volume tsdf (nz, ny, nx) fp32, weight (nz, ny, nx) uint8, vvalue (nz, ny, nx) fp32 of tsdf_integrate read
+    back in the nv cameras R (nv, 3, 3), t (nv, 3) (X_c = R X_w + t, 1 <= nv <= 64; any poses, not only the track's) with the intrinsics
+    K (3 x 3, host), the baseline and the image size = (h, w) (include/dis_hip.h, section "volumetric fusion"; tests/raycast_ref.py
+    restates it in numpy).  Every pixel's ray is sampled at the camera depths n step, n = 1, 2, ... (step: a length, default voxel, in
+    voxel / 8 .. 8 voxel); the first sample whose trilinear tsdf is negative, after a valid non-negative one, gives the crossing.
+    -> a dict of device tensors: disp (nv, h, w), the disparity of the crossing; normal (nv, 3, h, w), world axes, towards free space;
+    value (nv, h, w), the trilinear vvalue; all 0 where the ray meets no surface from observed free space.  A sample counts only where
+    the eight lattice points of its cell have weight >= min_weight (1 .. 4).  variant 0 skips free and unobserved space through a
+    byte per cell and a count per brick of 8 x 8 x 8 cells, variant 1 is the plain march; both give the same bits.  Up to three
+    launches on the current stream, no synchronisation; capturable when a workspace (uint8, at least
+    dis_tsdf_raycast_workspace(nx, ny, nz) bytes, 16-byte aligned) is given.  The inputs are data: no autograd."""
+    _chk(tsdf, vvalue, R, t)
+    if not (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.is_contiguous()):
+        raise RuntimeError('tsdf_raycast: weight must be a contiguous CUDA(HIP) tensor: the HIP path is the only path')
+    if tsdf.dim() != 3 or tuple(weight.shape) != tuple(tsdf.shape) or tuple(vvalue.shape) != tuple(tsdf.shape):
+        raise RuntimeError('tsdf_raycast: tsdf, weight and vvalue (nz, ny, nx) are expected')
+    if tsdf.dtype != torch.float32 or vvalue.dtype != torch.float32 or weight.dtype != torch.uint8:
+        raise RuntimeError('tsdf_raycast: tsdf and vvalue are float32, weight is uint8')
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or tuple(t.shape) != (int(R.shape[0]), 3):
+        raise RuntimeError('tsdf_raycast: R (nv, 3, 3) and t (nv, 3) are expected')
+    nz, ny, nx = (int(v) for v in tsdf.shape)
+    nv, h, w = int(R.shape[0]), int(size[0]), int(size[1])
+    need = lib.fn('dis_tsdf_raycast_workspace')(nx, ny, nz)
+    if need < 0 or not (1 <= nv <= 64 and 2 <= h <= 8192 and 2 <= w <= 8192):
+        raise lib.DisHipError(f'tsdf_raycast: unsupported extents nv={nv} h={h} w={w} nx={nx} ny={ny} nz={nz}')
+    voxel, baseline, min_weight, variant = float(voxel), float(baseline), int(min_weight), int(variant)
+    step = voxel if step is None else float(step)
+    origin = [float(origin[0]), float(origin[1]), float(origin[2])]
+    K4 = _k4(K)
+    if not (all(_fin(v) for v in K4 + origin + [voxel, baseline, step]) and voxel > 0 and K4[0] > 0 and K4[1] > 0 and baseline > 0
+            and 1 <= min_weight <= 4 and voxel / 8 <= step <= 8 * voxel and variant in (0, 1)):   # refused before anything is allocated
+        raise lib.DisHipError(f'tsdf_raycast: unsupported configuration voxel={voxel} step={step} origin={origin} K={K4} '
+                              f'baseline={baseline} min_weight={min_weight} variant={variant}')
+    dev = tsdf.device
+    workspace = _workspace('tsdf_raycast', need, workspace, dev)
+    res = {'disp': torch.empty((nv, h, w), dtype=torch.float32, device=dev), 'normal': torch.empty((nv, 3, h, w), dtype=torch.float32, device=dev),
+           'value': torch.empty((nv, h, w), dtype=torch.float32, device=dev)}
+    lib.call('dis_tsdf_raycast', tsdf, weight, vvalue, lib.host_floats(origin), voxel, min_weight, R, t, lib.host_floats(K4), baseline, step,
+             variant, res['disp'], res['normal'], res['value'], nv, h, w, nx, ny, nz, workspace, int(workspace.numel()))
+    return res

@@ -1036,7 +1036,7 @@ int dis_refine_track_poses(const float* disp, const float* flow, const float* K4
 /* ---------------------------------------------------------------- volumetric fusion --------- */
 
 /* The per-frame disparity maps of ONE track -> a truncated signed distance volume on a regular lattice, and the volume -> an indexed
- * triangle mesh by naive surface nets (csrc/tsdf.hip).  Conventions of "track rendering" and "track fusion": X_c = R X_w + t,
+ * triangle mesh by naive surface nets (csrc/tsdf.hip), or cast back into per-pixel maps of any camera (csrc/raycast.hip).  Conventions of "track rendering" and "track fusion": X_c = R X_w + t,
  * disp = fx baseline / z, a disparity is valid when it is finite and > 0.  fp32; tests/tsdf_ref.py restates both in numpy, operand
  * order included.  One track per call (a volume can fill the device); no atomics: two calls give the same bits.
  *
@@ -1104,6 +1104,49 @@ long dis_tsdf_mesh_workspace(int nx, int ny, int nz);
 int dis_tsdf_mesh(const float* tsdf, const unsigned char* weight, const float* vvalue, const float* origin3_host, float voxel,
                   int min_weight, int vcap, int fcap, const DisTsdfMeshOut* out, int nx, int ny, int nz, void* workspace,
                   long workspace_bytes, void* stream);
+
+/* dis_tsdf_raycast: the volume read back in a camera's view (csrc/raycast.hip): per pixel of nv views - they need not be the track's
+ * frames - the first crossing of the trilinear tsdf from free space into the surface along the pixel's ray.  tests/raycast_ref.py
+ * restates it in numpy, operand order included.  For the pixel (u, v) of view f, R = R_f, t = t_f:
+ *   ray       dc = ((float(u) - cx) / fx, (float(v) - cy) / fy, 1); the camera centre o_k = -((R[0][k] t0 + R[1][k] t1) + R[2][k] t2), the
+ *             direction d_k = (R[0][k] dc0 + R[1][k] dc1) + R[2][k]: the ray is parameterised by the camera depth z.
+ *   samples   anchored at the camera: z_n = float(n) step for n = 1 .. 2^24 - 1, formed from n for every sample on its own.  Lattice
+ *             coordinate g_a = ((o_a + z_n d_a) - origin_a) / voxel.  The sample is inside when 0 <= g_a < float(n_a - 1) on the three
+ *             axes, compared as floats (false for NaN); then i_a = floor(g_a), f_a = g_a - float(i_a).  It is valid when it is inside and
+ *             the eight corner weights of cell (i_x, i_y, i_z) are all >= min_weight.  s(n): the eight tsdf corners interpolated along
+ *             x, then y, then z, each as a + f (b - a).
+ *   march     n* = the smallest n with s(n) valid and s(n) < 0.  A hit: n* >= 2, s(n* - 1) valid and s(n* - 1) >= 0; then
+ *             z* = z_{n* - 1} + step (s0 / (s0 - s1)), disp = fb / z*, fb = fx baseline formed in fp32 on the host.  Every other ray - no
+ *             n*, a start inside or behind a surface, a surface reached out of unobserved space - is a miss: 0 in all three outputs.
+ *   normal    the gradient of the trilinear interpolant at sample n* in its cell, corners c_xyz: dx_yz = c_1yz - c_0yz,
+ *             c_yz = c_0yz + f_x dx_yz, dy_z = c_1z - c_0z, c_z = c_0z + f_y dy_z;
+ *             g0 = gx_0 + f_z (gx_1 - gx_0) with gx_z = dx_0z + f_y (dx_1z - dx_0z), g1 = dy_0 + f_z (dy_1 - dy_0), g2 = c_1 - c_0; divided
+ *             by sqrt((g0 g0 + g1 g1) + g2 g2): world axes, towards positive tsdf (free space) as the mesh normals; zeros when that length
+ *             is zero or not finite.
+ *   value     the trilinear vvalue at sample n*.  (Normal and value are taken at the first sample behind the surface, at most one step
+ *             from it.)
+ * tsdf, weight, vvalue (nz, ny, nx) as dis_tsdf_integrate writes them, R (nv, 3, 3), t (nv, 3): DEVICE.  origin3_host, K4_host: HOST.
+ * Outputs, DEVICE, every element written: disp (nv, h, w), normal (nv, 3, h, w), value (nv, h, w), fp32.
+ * variant 1, the plain form: one launch; every sample of a ray's range of n - a slab test against the lattice box, widened on both
+ * sides; a sample outside the lattice is invalid, so the widening changes no result - reads its eight weights and eight corners.
+ * variant 0, the shipped form, gives the same bits from three launches: the state of every cell (0: a corner weight below min_weight,
+ * 1: all observed and none negative, 2: all observed and one negative; a + f (b - a) cannot be negative between non-negative corners, so
+ * only state-2 cells are gathered), the number of state-2 cells of every brick of 8 x 8 x 8 cells (a ray inside a brick without one
+ * jumps to its last sample that still lies inside that brick), the march.  A wave takes an 8 x 8 tile of pixels.
+ * No atomics, no allocation, no synchronisation: two calls give the same bits, and the call is capturable.
+ * workspace: dis_tsdf_raycast_workspace(nx, ny, nz) BYTES (-1: unsupported extents), 16-byte aligned, no initialisation; after a call
+ * of variant 0 it holds the cell states (nz - 1, ny - 1, nx - 1) uint8 at byte 0 and, at the next multiple of 16, the state-2 counts of
+ * the bricks (ceil((nz - 1) / 8), ceil((ny - 1) / 8), ceil((nx - 1) / 8)) int32.
+ * Checks, in this order, all before any launch: a NULL pointer -> DIS_ERR_NULL; nv outside 1 .. 64, h or w outside 2 .. 8192, nx, ny or nz
+ * outside 2 .. 1024 -> DIS_ERR_BAD_SHAPE; fx, fy, baseline, fx baseline or voxel not positive and finite, cx, cy or a component of the
+ * origin not finite, min_weight outside 1 .. 4, step outside voxel / 8 .. 8 voxel, (the lattice's diagonal in voxels) voxel / step - a
+ * bound on the samples a ray has inside the lattice - not below 2^24 (float(n) must stay exact), workspace_bytes below
+ * dis_tsdf_raycast_workspace(...), a misaligned workspace, a variant other than 0 or 1 -> DIS_ERR_UNSUPPORTED. */
+long dis_tsdf_raycast_workspace(int nx, int ny, int nz);
+int dis_tsdf_raycast(const float* tsdf, const unsigned char* weight, const float* vvalue, const float* origin3_host, float voxel,
+                     int min_weight, const float* R, const float* t, const float* K4_host, float baseline, float step, int variant,
+                     float* disp, float* normal, float* value, int nv, int h, int w, int nx, int ny, int nz, void* workspace,
+                     long workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
