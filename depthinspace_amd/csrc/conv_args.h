@@ -1,5 +1,5 @@
 // Argument blocks of the convolution kernels and the declarations of their launchers: shared by conv2d.hip (the entry points) and the
-// kernel files (conv_f16x2.hip, conv_gen.hip, conv_bf16.hip, conv_k4s2.hip, conv1x1_bwd_fused.hip and the three one-launch 3x3 backward files
+// kernel files (conv_f16x2.hip, conv_gen.hip, conv_bf16.hip, conv_stream_wgrad.hip, conv_k4s2.hip, conv1x1_bwd_fused.hip and the three one-launch 3x3 backward files
 // conv_bwd_fused*.hip, whose common parts are in conv_bwd_fused_common.h).
 #pragma once
 #include "common.h"
@@ -159,6 +159,18 @@ __device__ __forceinline__ float dis_copy_w_rows(const float* w, int w_o, int ro
 }
 
 // ------------------------------------------------------------------------------------------------
+// bf16 activation storage (conv_bf16.hip, conv_stream_wgrad.hip): a bf16 value is the upper half of the fp32 with the same value
+// ------------------------------------------------------------------------------------------------
+typedef unsigned short bf16_t;
+
+__device__ __forceinline__ unsigned cb_pack2(float a, float b) {
+  const f32x2 v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));  // v_cvt_pk_bf16_f32: round to nearest even
+}
+__device__ __forceinline__ float cb_lo(unsigned p) { return __uint_as_float(p << 16); }
+__device__ __forceinline__ float cb_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
+
+// ------------------------------------------------------------------------------------------------
 // two-term fp16 split ("f16x2": conv_f16x2.hip, conv_gen.hip): x * 2^s = h1 + h2, 11 + 11 significant bits
 // ------------------------------------------------------------------------------------------------
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
@@ -230,7 +242,7 @@ hipError_t dis_f2_wgrad_k4s2_launch(const WgArgs& a, int gnb_act, long workers, 
 bool dis_f2_enabled();
 int dis_f2_wgrad_wpc();   // workgroups per CU the two-term weight-gradient kernel is built for
 
-// conv2d.hip, called from the streaming dispatchers (conv_gen.hip, conv_bf16.hip): 3x3 stride-1 layers as 32 x 32 channel-slice
+// conv2d.hip, called from the streaming dispatchers (conv_gen.hip, conv_bf16.hip, conv_stream_wgrad.hip): 3x3 stride-1 layers as 32 x 32 channel-slice
 // launches of the halo-resident bf16x3 kernel ...
 long dis_bx_slices_ok(int n, int h, int wd, int cin, int cout, int ldx, int ldy, int xoff, int yoff, int k, int stride,
                       int pad, int act);

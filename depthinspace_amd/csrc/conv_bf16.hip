@@ -11,27 +11,17 @@
 //       x is bf16 (XB) or fp32 (network input, head gradient), y is bf16 (YB) or fp32 (head pre-activation).
 //       The weights are the MFMA's A operand and the pixels its B operand, so a lane ends up with 4 consecutive output
 //       channels of one pixel: one 8-byte (bf16) / 16-byte (fp32) store.
-//   convb_wgrad_kernel<MTW, NTW, XB, GB>   weight gradient: split-K slabs over pixel ranges, fp32 MFMA on the values the
-//       bf16 tensors hold (exact products of bf16 values, fp32 accumulation), fp64 slab sums.
+//   (the weight gradient - dis_convb_wgrad - is in conv_stream_wgrad.hip, shared with the fp32 storage)
 //   element-wise helpers on bf16 nhwc tensors (activation gradient, channel copies, column sums).
 #include "conv_args.h"
 #include "conv_plan.h"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef unsigned short bf16_t;
-
 #define CB_MAXTAPS 49
 #define CB_BM 128
 #define CB_CK 32
 #define CB_AS 40  // LDS pixel stride of the A tile (16-bit units): 32 channels + 8 pad (16 consecutive pixels: 16 distinct slots)
-
-__device__ __forceinline__ unsigned cb_pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));  // v_cvt_pk_bf16_f32: round to nearest even
-}
-__device__ __forceinline__ float cb_lo(unsigned p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float cb_hi(unsigned p) { return __uint_as_float(p & 0xffff0000u); }
 
 struct GenArgsB {
   const void* x;
@@ -1250,297 +1240,6 @@ extern "C" int dis_convb_run(int mode, const void* x, int x_bf16, int ldx, int x
                        [&](const GenArgsB& b, int slice, long s_ci, long s_co, const short* tsrc, bool halo_only) {
                          return cb_run(b, x_bf16, y_bf16, w, wp + slice * pstride, cin_w, cout_w, s_ci, s_co, tsrc, s, halo_only);
                        });
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight gradient: dW[tap][xc][gc] = sum_pixels X[pixel + tap][xc] * G[pixel][gc], X / G bf16 or fp32
-// (structure of convg_wgrad_kernel: one tap x TX x-channels x TG g-channels per workgroup, 32 pixels per step, split-K slabs)
-// ------------------------------------------------------------------------------------------------
-struct WgArgsB {
-  const void* X;
-  const void* G;
-  float* part;  // [ksplit][tap][cXp][cGp]
-  int n, hX, wX, ldX, xoff, cX;
-  int hG, wG, ldG, goff, cG;
-  int S, pad, k;
-  int nxb, ngb;
-  int mper;
-  int cXp, cGp;
-};
-template <bool BF>
-__device__ __forceinline__ float4 cb_load4(const void* p, long e) {
-  if (BF) {
-    const uint2 v = *(const uint2*)((const bf16_t*)p + e);
-    return make_float4(cb_lo(v.x), cb_hi(v.x), cb_lo(v.y), cb_hi(v.y));
-  }
-  return *(const float4*)((const float*)p + e);
-}
-template <int MTW, int NTW, bool XB, bool GB>
-__global__ __launch_bounds__(256) void convb_wgrad_kernel(WgArgsB a) {
-  constexpr int TX = 32 * MTW, TG = 32 * NTW, XS = TX + 16, GS = TG + 16;
-  constexpr int X_FL = 32 * XS, G_FL = 32 * GS;
-  constexpr int NLX = TX / 32, NLG = TG / 32;
-  __shared__ __attribute__((aligned(16))) float smem[2 * (X_FL + G_FL)];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
-  const int ntaps = a.k * a.k;
-  const int tap = blockIdx.x % ntaps;
-  const int rest = blockIdx.x / ntaps;
-  const int xb = rest % a.nxb, gb = rest / a.nxb;
-  const int ky = tap / a.k, kx = tap % a.k;
-  const int M = a.n * a.hG * a.wG;
-  const int m_lo = blockIdx.y * a.mper;
-  const int m_hi = min(M, m_lo + a.mper);
-  float4 rx[NLX], rg[NLG];
-  auto prefetch = [&](int mbase) {
-#pragma unroll
-    for (int j = 0; j < NLX; ++j) {
-      const int item = tid + j * 256;
-      const int px = item / (TX / 4), q = item % (TX / 4);
-      const int m = mbase + px;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int c = xb * TX + q * 4;
-      if (m < m_hi && c < a.cX) {
-        const int gx = m % a.wG, t = m / a.wG, gy = t % a.hG, nn = t / a.hG;
-        const int iy = gy * a.S - a.pad + ky, ix = gx * a.S - a.pad + kx;
-        if (iy >= 0 && iy < a.hX && ix >= 0 && ix < a.wX)
-          v = cb_load4<XB>(a.X, (((long)nn * a.hX + iy) * a.wX + ix) * a.ldX + a.xoff + c);
-      }
-      rx[j] = v;
-    }
-#pragma unroll
-    for (int j = 0; j < NLG; ++j) {
-      const int item = tid + j * 256;
-      const int px = item / (TG / 4), q = item % (TG / 4);
-      const int m = mbase + px;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      const int c = gb * TG + q * 4;
-      if (m < m_hi && c < a.cG) v = cb_load4<GB>(a.G, (long)m * a.ldG + a.goff + c);
-      rg[j] = v;
-    }
-  };
-  auto stage = [&](int buf) {
-    float* Xt = smem + buf * (X_FL + G_FL);
-    float* Gt = Xt + X_FL;
-#pragma unroll
-    for (int j = 0; j < NLX; ++j) {
-      const int item = tid + j * 256;
-      *(float4*)(Xt + (item / (TX / 4)) * XS + (item % (TX / 4)) * 4) = rx[j];
-    }
-#pragma unroll
-    for (int j = 0; j < NLG; ++j) {
-      const int item = tid + j * 256;
-      *(float4*)(Gt + (item / (TG / 4)) * GS + (item % (TG / 4)) * 4) = rg[j];
-    }
-  };
-  f32x4 acc[MTW][NTW];
-#pragma unroll
-  for (int mt = 0; mt < MTW; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  const int wx = wave & 1, wg = wave >> 1;
-  if (m_lo < m_hi) {
-    prefetch(m_lo);
-    stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int mb = m_lo; mb < m_hi; mb += 32) {
-      const bool more = mb + 32 < m_hi;
-      if (more) prefetch(mb + 32);
-      const float* Xt = smem + buf * (X_FL + G_FL);
-      const float* Gt = Xt + X_FL;
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        float av[MTW], bv[NTW];
-#pragma unroll
-        for (int mt = 0; mt < MTW; ++mt) av[mt] = Xt[(kk * 4 + lg) * XS + wx * 16 * MTW + mt * 16 + li];
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) bv[nt] = Gt[(kk * 4 + lg) * GS + wg * 16 * NTW + nt * 16 + li];
-#pragma unroll
-        for (int mt = 0; mt < MTW; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt)
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
-      }
-      if (more) stage(buf ^ 1);
-      __syncthreads();
-      buf ^= 1;
-    }
-  }
-  float* out = a.part + ((long)blockIdx.y * ntaps + tap) * a.cXp * a.cGp;
-#pragma unroll
-  for (int mt = 0; mt < MTW; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int xc = xb * TX + wx * 16 * MTW + mt * 16 + lg * 4 + r;
-        const int gc = gb * TG + wg * 16 * NTW + nt * 16 + li;
-        out[(long)xc * a.cGp + gc] = acc[mt][nt][r];
-      }
-}
-__global__ void convb_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw, int nsplit, int ntaps,
-                                          int cXp, int cGp, int cXw, int cGw) {
-  const long total = (long)ntaps * cXw * cGw;
-  const long slab = (long)ntaps * cXp * cGp;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int g = (int)(i % cGw);
-    long r = i / cGw;
-    const int x = (int)(r % cXw);
-    const int tap = (int)(r / cXw);
-    const float* p = part + ((long)tap * cXp + x) * cGp + g;
-    double s = 0.0;
-    for (int k = 0; k < nsplit; ++k) s += (double)p[k * slab];
-    gw[((long)g * cXw + x) * ntaps + tap] = (float)s;
-  }
-}
-// ---- weight gradient of a disparity head: ONE gradient channel (cG_w = 1), 3x3, stride 1, x bf16 ----
-// dW[tap][c] = sum_o x[o + tap - pad][c] * g[o] is a reduction with 9 cX outputs: no matrix core needed, HBM-bound on the one
-// read of x.  Thread = (8-channel chunk, pixel slot): per x pixel one 16-byte load and 9 gradient scalars (neighbouring
-// output pixels: served by L1 / L2), 72 register accumulators; lanes of a chunk are folded with xor-shuffles, waves through LDS,
-// workgroups through [block][tap][cX] slabs finished by convb_head_reduce_kernel (fp64, fixed order: deterministic).
-#define CBH_BLOCKS 512
-template <int C8, bool GB>
-__global__ __launch_bounds__(256) void convb_head_wgrad_kernel(const bf16_t* __restrict__ X, int ldX, int xoff,
-                                                               const void* __restrict__ G, int ldG, int goff,
-                                                               float* __restrict__ part, int n, int h, int w, int pad) {
-  constexpr int PPB = 256 / C8, CX = 8 * C8;
-  __shared__ float red[4][9 * CX];
-  const int chunk = threadIdx.x % C8, slot = threadIdx.x / C8;
-  float acc[9][8];
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[t][j] = 0.f;
-  const long npix = (long)n * h * w;
-  for (long p = (long)blockIdx.x * PPB + slot; p < npix; p += (long)gridDim.x * PPB) {
-    const int xx = (int)(p % w);
-    const long r = p / w;
-    const int yy = (int)(r % h);
-    const uint4 v = *(const uint4*)(X + p * ldX + xoff + chunk * 8);
-    const float xv[8] = {cb_lo(v.x), cb_hi(v.x), cb_lo(v.y), cb_hi(v.y), cb_lo(v.z), cb_hi(v.z), cb_lo(v.w), cb_hi(v.w)};
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const int oy = yy - ky + pad, ox = xx - kx + pad;
-        float g = 0.f;
-        if ((unsigned)oy < (unsigned)h && (unsigned)ox < (unsigned)w) {
-          const long o = p + (long)(pad - ky) * w + (pad - kx);
-          g = GB ? __uint_as_float((unsigned)((const bf16_t*)G)[o * ldG + goff] << 16) : ((const float*)G)[o * ldG + goff];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[ky * 3 + kx][j] = fmaf(g, xv[j], acc[ky * 3 + kx][j]);
-      }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float a = acc[t][j];
-#pragma unroll
-      for (int m = C8; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
-      if (lane < C8) red[wave][t * CX + chunk * 8 + j] = a;
-    }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 9 * CX; i += 256)
-    part[(long)blockIdx.x * (9 * CX) + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-}
-// gw[0][x][tap] = sum over the workgroup slabs, one wave per output (lanes stride over the slabs in fp64, fixed fold order)
-__global__ __launch_bounds__(256) void convb_head_reduce_kernel(const float* __restrict__ part, float* __restrict__ gw,
-                                                                int nslab, int cX, int cXw) {
-  const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (o >= 9 * cXw) return;
-  const int tap = o / cXw, x = o % cXw;
-  double s = 0.0;
-  for (int k = lane; k < nslab; k += 64) s += (double)part[(long)k * (9 * cX) + tap * cX + x];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  if (lane == 0) gw[(long)x * 9 + tap] = (float)s;
-}
-static bool cbh_eligible(int x_bf16, int cX, int cG_w, int k, int stride, int ldX, int xoff) {
-  return x_bf16 && cG_w == 1 && k == 3 && stride == 1 && (cX == 16 || cX == 32 || cX == 64 || cX == 128) &&
-         !((ldX | xoff) & 7);
-}
-template <bool GB>
-static void cbh_launch(int c8, int blocks, const void* X, int ldX, int xoff, const void* G, int ldG, int goff, float* part,
-                       int n, int h, int w, int pad, hipStream_t s) {
-#define CBH_CASE(C8_) \
-  if (c8 == C8_)      \
-    hipLaunchKernelGGL((convb_head_wgrad_kernel<C8_, GB>), dim3(blocks), dim3(256), 0, s, (const bf16_t*)X, ldX, xoff, G, ldG, \
-                       goff, part, n, h, w, pad);
-  CBH_CASE(2) CBH_CASE(4) CBH_CASE(8) CBH_CASE(16)
-#undef CBH_CASE
-}
-
-extern "C" long dis_convb_wgrad_workspace(int n, int hG, int wG, int cX, int cG, int k) {
-  if (n <= 0 || hG <= 0 || wG <= 0 || cX <= 0 || cG <= 0 || k <= 0 || k * k > CB_MAXTAPS) return -1;
-  const WgradSplitPlan p = wgrad_split_plan(n, hG, wG, cX, cG, k);
-  const long f32 = (long)p.nsplit * k * k * (p.nxb * 32 * p.mtw) * (p.ngb * 32 * p.ntw);
-  // (the slice-pair form, if dis_convb_wgrad takes it for this layer: the stride is not known here, so size for both)
-  const long b1 = dis_wgrad_pairs_workspace(n, 1, 1, hG, wG, cX, cG, 8, 8, k, 1, 1);
-  const long b2 = dis_wgrad_pairs_workspace(n, 1, 1, hG, wG, cX, cG, 8, 8, k, 2, 1);
-  long b3 = b1 > b2 ? b1 : b2;
-  if (cG <= 4 && k == 3 && b3 < (long)CBH_BLOCKS * 9 * cX) b3 = (long)CBH_BLOCKS * 9 * cX;  // head form
-  return b3 > f32 ? b3 : f32;
-}
-template <bool XB, bool GB>
-static void cbw_launch(const WgArgsB& a, int mtw, int ntw, dim3 grid, hipStream_t s) {
-  if (mtw == 2 && ntw == 2) hipLaunchKernelGGL((convb_wgrad_kernel<2, 2, XB, GB>), grid, dim3(256), 0, s, a);
-  else if (mtw == 2) hipLaunchKernelGGL((convb_wgrad_kernel<2, 1, XB, GB>), grid, dim3(256), 0, s, a);
-  else if (ntw == 2) hipLaunchKernelGGL((convb_wgrad_kernel<1, 2, XB, GB>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((convb_wgrad_kernel<1, 1, XB, GB>), grid, dim3(256), 0, s, a);
-}
-// argument meaning of dis_convg_wgrad (conv_gen.hip); ld / offsets in elements; x_bf16 / g_bf16 as in dis_convb_run
-extern "C" int dis_convb_wgrad(const void* X, int x_bf16, int ldX, int xoff, int hX, int wX, int cX, int cX_w, const void* G,
-                               int g_bf16, int ldG, int goff, int hG, int wG, int cG, int cG_w, float* grad_w,
-                               float* workspace, int n, int k, int stride, int pad, void* stream) {
-  if (!X || !G || !grad_w || !workspace) return DIS_ERR_NULL;
-  if (n <= 0 || hX <= 0 || wX <= 0 || hG <= 0 || wG <= 0 || cX <= 0 || cG <= 0 || cX_w <= 0 || cG_w <= 0 || cX_w > cX ||
-      cG_w > cG || k <= 0 || pad < 0)
-    return DIS_ERR_BAD_SHAPE;
-  if ((cX & 3) || (cG & 3) || (xoff & 3) || (goff & 3) || (ldX & 3) || (ldG & 3) || xoff + cX > ldX || goff + cG > ldG)
-    return DIS_ERR_BAD_SHAPE;
-  if (k * k > CB_MAXTAPS || (stride != 1 && stride != 2)) return DIS_ERR_UNSUPPORTED;
-  if ((long)n * hG * wG > 2147483647L - 64) return DIS_ERR_BAD_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  if (x_bf16 && g_bf16 && !((xoff | goff) & 7) && xoff + ((cX + 7) & ~7) <= ldX && goff + ((cG + 7) & ~7) <= ldG &&
-      dis_wgrad_pairs_workspace(n, hX, wX, hG, wG, cX, cG, ldX, ldG, k, stride, 1) >= 0)
-    return dis_wgrad_pairs_run((const float*)X, ldX, xoff, hX, wX, cX, cX_w, (const float*)G, ldG, goff, hG, wG, cG,
-                               cG_w, grad_w, workspace, n, k, stride, pad, 1, s);
-  if (cbh_eligible(x_bf16, cX, cG_w, k, stride, ldX, xoff) && hX == hG && wX == wG) {
-    const long npix = (long)n * hG * wG;
-    const int c8 = cX / 8, ppb = 256 / c8;
-    long blocks = (npix + ppb - 1) / ppb;
-    if (blocks > CBH_BLOCKS) blocks = CBH_BLOCKS;
-    if (g_bf16) cbh_launch<true>(c8, (int)blocks, X, ldX, xoff, G, ldG, goff, workspace, n, hG, wG, pad, s);
-    else cbh_launch<false>(c8, (int)blocks, X, ldX, xoff, G, ldG, goff, workspace, n, hG, wG, pad, s);
-    const long tot = 9L * cX_w;
-    hipLaunchKernelGGL(convb_head_reduce_kernel, dim3((unsigned)((tot + 3) / 4)), dim3(256), 0, s, (const float*)workspace,
-                       grad_w, (int)blocks, cX, cX_w);
-    DIS_CHECK_LAUNCH();
-    return DIS_OK;
-  }
-  WgArgsB a;
-  a.X = X; a.G = G; a.part = workspace;
-  a.n = n; a.hX = hX; a.wX = wX; a.ldX = ldX; a.xoff = xoff; a.cX = cX;
-  a.hG = hG; a.wG = wG; a.ldG = ldG; a.goff = goff; a.cG = cG;
-  a.S = stride; a.pad = pad; a.k = k;
-  const WgradSplitPlan p = wgrad_split_plan(n, hG, wG, cX, cG, k);
-  const int nsplit = p.nsplit, mtw = p.mtw, ntw = p.ntw;
-  a.nxb = p.nxb; a.ngb = p.ngb; a.mper = p.mper;
-  a.cXp = a.nxb * 32 * mtw;
-  a.cGp = a.ngb * 32 * ntw;
-  const dim3 grid((unsigned)(k * k * a.nxb * a.ngb), (unsigned)nsplit);
-  if (x_bf16 && g_bf16) cbw_launch<true, true>(a, mtw, ntw, grid, s);
-  else if (x_bf16) cbw_launch<true, false>(a, mtw, ntw, grid, s);
-  else if (g_bf16) cbw_launch<false, true>(a, mtw, ntw, grid, s);
-  else cbw_launch<false, false>(a, mtw, ntw, grid, s);
-  const long total = (long)k * k * cX_w * cG_w;
-  hipLaunchKernelGGL(convb_wgrad_reduce_kernel, dim3(dis_ew_grid(total, 256)), dim3(256), 0, s, (const float*)workspace,
-                     grad_w, nsplit, k * k, a.cXp, a.cGp, cX_w, cG_w);
-  DIS_CHECK_LAUNCH();
-  return DIS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

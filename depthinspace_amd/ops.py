@@ -1951,31 +1951,31 @@ class _CatFrom(torch.autograd.Function):
         return (None, None) + tuple(g[..., o:o + c] for o, c in zip(ctx.offs, ctx.cs))
 
 
-class _WriteChannels(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, src, slot, zero_tail):
-        buf, off, c = slot
-        n, h, w, cs = src.shape
-        assert cs == c and tuple(buf.shape[:3]) == (n, h, w)
-        src = _nhwc(src)
-        if not src.is_cuda or src.dtype != torch.float32:
-            raise RuntimeError('depthinspace_amd ops need float32 CUDA(HIP) tensors: the HIP path is the only path')
-        dst = buf[..., off:off + c]
-        lib.call('dis_copy_channels', src, _ld(src), dst, buf.shape[3], n * h * w, c,
-                 buf.shape[3] - off - c if zero_tail else 0)
-        return dst
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None, None
+# --------------------------------------------------------------------------------------------------
+# The streaming convolutions of DispNetS for two activation storages: fp32 (csrc/conv_gen.hip), and bf16 (BASELINE config 2;
+# csrc/conv_bf16.hip): nhwc feature maps are torch.bfloat16 - one bf16 product per MAC, fp32 accumulation - while parameters,
+# parameter gradients and disparities stay float32.  One autograd path serves both; a _Storage carries what differs.
+# --------------------------------------------------------------------------------------------------
+BF16 = torch.bfloat16
 
 
-def write_channels(src, slot, zero_tail=False):
-    """copy the nhwc tensor src into a ConcatBuf slot; returns the slot's view (differentiable).  zero_tail: also zero the
-    buffer's padding lanes behind the slot (the slot must be the concatenation's last part)."""
-    if slot[0].dtype == torch.bfloat16:
-        return _WriteChannelsB.apply(src, slot, zero_tail)
-    return _WriteChannels.apply(src, slot, zero_tail)
+def _isbf(t):
+    return 1 if t.dtype == BF16 else 0
+
+
+def _chk_f32(x):
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise RuntimeError('depthinspace_amd ops need float32 CUDA(HIP) tensors: the HIP path is the only path')
+
+
+def _chk_act(*ts):
+    for t in ts:
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype not in (torch.float32, BF16):
+            raise RuntimeError('depthinspace_amd bf16 ops need float32 / bfloat16 CUDA(HIP) tensors: the HIP path is the only path')
+        if _ld(t) is None or (t.dtype == BF16 and _ld(t) % 8):
+            raise RuntimeError('expected a dense nhwc tensor or a channel range of one (bf16: channels in multiples of 8)')
 
 
 def _convg_run(mode, x, w, bias, y, n, hin, win, cin, cin_w, hout, wout, cout, cout_w, k, stride, pad, act):
@@ -1987,231 +1987,6 @@ def _convg_run(mode, x, w, bias, y, n, hin, win, cin, cin_w, hout, wout, cout, c
     wp = torch.empty(per * phases + max(sk, 0), dtype=torch.float32, device=x.device)
     lib.call('dis_convg_run', mode, x, _ld(x), 0, w, bias, y, _ld(y), 0, wp, n, hin, win, cin, cin_w, hout,
              wout, cout, cout_w, k, stride, pad, act)
-
-
-def _convg_wgrad(X, hX, wX, cX, cX_w, G, hG, wG, cG, cG_w, gw, n, k, stride, pad):
-    wsz = lib.fn('dis_convg_wgrad_workspace')(n, hG, wG, cX, cG, k)
-    if wsz < 0:
-        raise lib.DisHipError('convg wgrad: unsupported shape')
-    ws = torch.empty(wsz, dtype=torch.float32, device=X.device)
-    lib.call('dis_convg_wgrad', X, _ld(X), 0, hX, wX, cX, cX_w, G, _ld(G), 0, hG, wG, cG, cG_w, gw, ws, n, k,
-             stride, pad)
-
-
-def _colsum(G, c_real, out=None):
-    """sum over all pixels of the first c_real channels of an nhwc tensor (into `out` if given)"""
-    ld = _ld(G)
-    npix = G.shape[0] * G.shape[1] * G.shape[2]
-    if out is None:
-        out = torch.empty(c_real, dtype=torch.float32, device=G.device)
-    ws = torch.empty(lib.fn('dis_colsum_workspace')(c_real), dtype=torch.float32, device=G.device)
-    lib.call('dis_colsum', G, ld, 0, npix, c_real, out, ws)
-    return out
-
-
-def _conv_stream_shapes(name, x, weight, stride, pad, transposed, out_hw, out, dtype, cmult):
-    """Shapes of a _ConvG / _ConvB forward and its output y of storage type `dtype` (cout a multiple of cmult): a new tensor, or
-    the ConcatBuf slot `out` = (buffer, channel offset, channels).  -> (n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y)"""
-    n, hin, win, cin_mem = x.shape
-    if transposed:
-        cin_w, cout, k, _ = weight.shape
-        hout, wout = out_hw
-        if stride != 2 or hout > 2 * hin or wout > 2 * win:
-            raise RuntimeError('transposed conv: stride 2 and out_hw <= 2x input expected')
-    else:
-        cout, cin_w, k, _ = weight.shape
-        hout, wout = (hin + 2 * pad - k) // stride + 1, (win + 2 * pad - k) // stride + 1
-    fp32 = dtype == torch.float32   # (bf16 storage: _chk_act has checked x; its buffers are told apart from fp32 ones by dtype)
-    if (fp32 and cin_mem % 4) or cin_w > cin_mem or cout % cmult:
-        raise RuntimeError(f'{name}: bad channel counts cin_mem={cin_mem} cin_w={cin_w} cout={cout}')
-    if out is None:
-        y = torch.empty((n, hout, wout, cout), dtype=dtype, device=x.device)
-    else:
-        buf, off, c = out
-        if c != cout or tuple(buf.shape[:3]) != (n, hout, wout) or (not fp32 and buf.dtype != dtype):
-            raise RuntimeError(f'{name}: out slot {tuple(buf.shape)}[{off}:{off + c}] does not fit ({n},{hout},{wout},{cout})')
-        y = buf[..., off:off + c]
-    return n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y
-
-
-class _ConvG(torch.autograd.Function):
-    """Conv2d / ConvTranspose2d(k,s2,p,op=1, cropped to out_hw) + bias + activation on nhwc tensors.
-    x (n,h,w,cin_mem): cin_mem % 4 == 0 and >= the weight's input channels (extra channels must be zero-weight
-    padding lanes; their gradient is returned as zeros)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, act, transposed, out_hw, need_dgrad, out=None):
-        x, weight = _nhwc(x), _c(weight)  # (x may be a channel range of a ConcatBuf)
-        _chk(weight, bias)
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise RuntimeError('depthinspace_amd ops need float32 CUDA(HIP) tensors: the HIP path is the only path')
-        n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y = _conv_stream_shapes(
-            'convg', x, weight, stride, pad, transposed, out_hw, out, torch.float32, 4)
-        _convg_run(CONVG_TCONV if transposed else CONVG_CONV, x, weight, bias, y, n, hin, win, cin_mem, cin_w, hout,
-                   wout, cout, cout, k, stride, pad, act)
-        ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
-        ctx.bias_ref = bias  # (gradient sink lookup)
-        ctx.cfg = (stride, pad, act, transposed, bias is not None, need_dgrad)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight, y = ctx.saved_tensors
-        stride, pad, act, transposed, has_bias, need_dgrad = ctx.cfg
-        n, hin, win, cin_mem = x.shape
-        gy = _nhwc(gy)
-        _, hout, wout, cout = gy.shape
-        k = weight.shape[2]
-        cin_w = weight.shape[0] if transposed else weight.shape[1]
-        # (shapes whose weight gradient runs on the one-pass kernels of conv2d.hip get their bias gradient from that pass)
-        onepass = (not transposed and x.is_contiguous()
-                   and lib.fn('dis_conv2d_wgrad_workspace')(cin_mem, cout, k, stride) >= 0)
-        gb, gb_ret = _sink_opt(ctx.bias_ref)
-        gb_done = False
-        if act != ACT_NONE or not gy.is_contiguous():
-            # (gy / y may be channel ranges of wider buffers: the gradient of a concatenation, an output written into one)
-            gpre = torch.empty(gy.shape, dtype=torch.float32, device=gy.device)
-            if has_bias and not onepass and cout <= 1024 and 256 % (cout // 4) == 0 and gy.data_ptr() % 16 == 0 \
-                    and (y is None or y.data_ptr() % 16 == 0):
-                # activation gradient and bias gradient from one pass over gy
-                gb_done = True
-                ws = torch.empty(lib.fn('dis_act_bwd_ld_bias_workspace')(cout), dtype=torch.float32, device=gy.device)
-                lib.call('dis_act_bwd_ld_bias', gy, _ld(gy), y, _ld(y) if y is not None else 0, gpre, act, n * hout * wout,
-                         cout, gb, ws)
-            elif gy.is_contiguous() and (y is None or y.is_contiguous()):
-                lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
-            else:
-                lib.call('dis_act_bwd_ld', gy, _ld(gy), y, _ld(y) if y is not None else 0, gpre, act, n * hout * wout, cout)
-        else:
-            gpre = gy
-        gx = None
-        if need_dgrad and ctx.needs_input_grad[0]:
-            gx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-            _convg_run(CONVG_TCONV_DGRAD if transposed else CONVG_CONV_DGRAD, gpre, weight, None, gx, n, hout, wout,
-                       cout, cout, hin, win, cin_mem, cin_w, k, stride, pad, ACT_NONE)
-        gw, gw_ret = _sink(weight)
-        if transposed:
-            _convg_wgrad(gpre, hout, wout, cout, cout, x, hin, win, cin_mem, cin_w, gw, n, k, stride, pad)
-        else:
-            # shapes whose whole (tap, cin) x cout accumulator fits a workgroup's registers go through the one-pass kernels
-            # of conv2d.hip (x and gy are read once instead of once per tap; the bias gradient comes out of the same pass)
-            if onepass:
-                wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin_mem, cout, k, stride)
-                ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
-                _conv_wgrad_any(x, gpre, gw, gb, ws, n, hin, win, cin_mem, cin_w, cout, k, stride, pad)
-                _sinks_written()
-                return gx, gw_ret, gb_ret, None, None, None, None, None, None, None
-            _convg_wgrad(x, hin, win, cin_mem, cin_w, gpre, hout, wout, cout, cout, gw, n, k, stride, pad)
-        if has_bias and not gb_done:
-            _colsum(gpre, cout, out=gb)
-        _sinks_written()
-        return gx, gw_ret, gb_ret, None, None, None, None, None, None, None
-
-
-def convg(x, weight, bias, stride=1, pad=0, act=ACT_NONE, need_dgrad=True, out=None, dtype=torch.float32):
-    """Conv2d on an nhwc tensor through the streaming MFMA kernel (any channel count that is a multiple of 4).
-    out: optional ConcatBuf.slot the result is written into (the returned tensor is that channel range).
-    dtype=torch.bfloat16: bf16 activation storage (the result is bf16; x bf16, or fp32 for the network input)."""
-    if dtype == torch.bfloat16:
-        return _ConvB.apply(x, weight, bias, stride, pad, act, False, None, need_dgrad, out)
-    return _ConvG.apply(x, weight, bias, stride, pad, act, False, None, need_dgrad, out)
-
-
-def convg_transposed(x, weight, bias, out_hw, pad=1, act=ACT_NONE, out=None, dtype=torch.float32):
-    """ConvTranspose2d(k=3, stride=2, padding=pad, output_padding=1) cropped to out_hw (crop_like)."""
-    if dtype == torch.bfloat16:
-        return _ConvB.apply(x, weight, bias, 2, pad, act, True, tuple(out_hw), True, out)
-    return _ConvG.apply(x, weight, bias, 2, pad, act, True, tuple(out_hw), True, out)
-
-
-def _head_stream_fwd(ctx, run, x, weight, bias, alpha, offset):
-    """A disparity head as a one-channel streaming conv (run: _convg_run / _convb_run) + alpha*sigmoid(. - offset); y is float32"""
-    n, h, w, cin = x.shape
-    k = weight.shape[2]
-    y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
-    run(CONVG_CONV, x, weight, bias, y.view(n, h, w, 1), n, h, w, cin, weight.shape[1], h, w, 1, 1, k, 1, k // 2, ACT_NONE)
-    lib.call('dis_sigmoid_affine_fwd', y, y, float(alpha), float(offset), y.numel())
-    ctx.save_for_backward(x, weight, y)
-    ctx.alpha = float(alpha)
-    ctx.bias_ref = bias
-    return y
-
-
-def _head_stream_bwd(ctx, run, wgrad, gy):
-    x, weight, y = ctx.saved_tensors
-    n, h, w, cin = x.shape
-    k = weight.shape[2]
-    cin_w = weight.shape[1]
-    gpre4 = torch.empty((n, h, w, 4), dtype=torch.float32, device=x.device)
-    lib.call('dis_sigmoid_affine_bwd', y, _c(gy), gpre4, ctx.alpha, n * h * w)
-    gx = torch.empty_like(x)
-    run(CONVG_CONV_DGRAD, gpre4, weight, None, gx, n, h, w, 4, 1, h, w, cin, cin_w, k, 1, k // 2, ACT_NONE)
-    gw, gw_ret = _sink(weight)
-    gb, gb_ret = _sink(ctx.bias_ref)
-    wgrad(x, h, w, cin, cin_w, gpre4, h, w, 4, 1, gw, n, k, 1, k // 2)
-    _colsum(gpre4, 1, out=gb)
-    _sinks_written()
-    return gx, gw_ret, gb_ret, None, None
-
-
-class _HeadG(torch.autograd.Function):
-    """Conv2d(cin,1,3,pad 1) + alpha*sigmoid(. - offset) for any cin % 4 == 0: x nhwc -> y planar (n,1,h,w)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, alpha, offset):
-        x, weight, bias = _c(x), _c(weight), _c(bias)
-        _chk(x, weight, bias)
-        n, h, w, cin = x.shape
-        ctx.direct = weight.shape[2] == 3 and cin in (16, 32) and weight.shape[1] == cin  # the one-pass head kernels (16 / 32 channels)
-        if ctx.direct:
-            y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
-            lib.call('dis_disp_head_fwd', x, weight, bias, y, n, h, w, cin, float(alpha), float(offset))
-            ctx.save_for_backward(x, weight, y)
-            ctx.alpha = float(alpha)
-            ctx.bias_ref = bias
-            return y
-        return _head_stream_fwd(ctx, _convg_run, x, weight, bias, alpha, offset)
-
-    @staticmethod
-    def backward(ctx, gy):
-        if not ctx.direct:
-            return _head_stream_bwd(ctx, _convg_run, _convg_wgrad, gy)
-        x, weight, y = ctx.saved_tensors
-        n, h, w, cin = x.shape
-        gw, gw_ret = _sink(weight)
-        gb, gb_ret = _sink(ctx.bias_ref)
-        gx = torch.empty_like(x)
-        ws = torch.empty(lib.fn('dis_disp_head_bwd_workspace')(n, h, w, cin), dtype=torch.float32, device=x.device)
-        lib.call('dis_disp_head_bwd', x, weight, y, _c(gy), gx, gw, gb, ws, n, h, w, cin, ctx.alpha)
-        _sinks_written()
-        return gx, gw_ret, gb_ret, None, None
-
-
-def disp_head_g(x, weight, bias, alpha, offset=3.0):
-    if x.dtype == torch.bfloat16:
-        return _HeadB.apply(x, weight, bias, alpha, offset)
-    return _HeadG.apply(x, weight, bias, alpha, offset)
-
-
-# --------------------------------------------------------------------------------------------------
-# DispNetS with bf16 activation storage (BASELINE config 2; csrc/conv_bf16.hip): nhwc feature maps are torch.bfloat16,
-# parameters / parameter gradients / disparities stay float32.  One bf16 product per MAC, fp32 accumulation.
-# --------------------------------------------------------------------------------------------------
-BF16 = torch.bfloat16
-
-
-def _isbf(t):
-    return 1 if t.dtype == BF16 else 0
-
-
-def _chk_act(*ts):
-    for t in ts:
-        if t is None:
-            continue
-        if not t.is_cuda or t.dtype not in (torch.float32, BF16):
-            raise RuntimeError('depthinspace_amd bf16 ops need float32 / bfloat16 CUDA(HIP) tensors: the HIP path is the only path')
-        if _ld(t) is None or (t.dtype == BF16 and _ld(t) % 8):
-            raise RuntimeError('expected a dense nhwc tensor or a channel range of one (bf16: channels in multiples of 8)')
 
 
 CONVB_PREPACKED = 0x100   # include/dis_hip.h DIS_CONVB_PREPACKED
@@ -2229,126 +2004,275 @@ def _convb_run(mode, x, w, bias, y, n, hin, win, cin, cin_w, hout, wout, cout, c
              wp, n, hin, win, cin, cin_w, hout, wout, cout, cout_w, k, stride, pad, act)
 
 
-def _convb_wgrad(X, hX, wX, cX, cX_w, G, hG, wG, cG, cG_w, gw, n, k, stride, pad):
-    wsz = lib.fn('dis_convb_wgrad_workspace')(n, hG, wG, cX, cG, k)
+def _wgrad(entry, X, hX, wX, cX, cX_w, G, hG, wG, cG, cG_w, gw, n, k, stride, pad):
+    """weight gradient through `entry` = dis_convg_wgrad (fp32 operands) or dis_convb_wgrad (each operand fp32 or bf16: it takes their
+    storage flags)"""
+    wsz = lib.fn(entry + '_workspace')(n, hG, wG, cX, cG, k)
     if wsz < 0:
-        raise lib.DisHipError('convb wgrad: unsupported shape')
+        raise lib.DisHipError(f'{entry}: unsupported shape')
     ws = torch.empty(wsz, dtype=torch.float32, device=X.device)
-    lib.call('dis_convb_wgrad', X, _isbf(X), _ld(X), 0, hX, wX, cX, cX_w, G, _isbf(G), _ld(G), 0, hG, wG, cG, cG_w, gw, ws,
-             n, k, stride, pad)
+    fx, fg = ((_isbf(X),), (_isbf(G),)) if entry == 'dis_convb_wgrad' else ((), ())
+    lib.call(entry, X, *fx, _ld(X), 0, hX, wX, cX, cX_w, G, *fg, _ld(G), 0, hG, wG, cG, cG_w, gw, ws, n, k, stride, pad)
 
 
-def _colsum_b(G, c_real, out=None):
-    npix = G.shape[0] * G.shape[1] * G.shape[2]
-    if out is None:
-        out = torch.empty(c_real, dtype=torch.float32, device=G.device)
-    ws = torch.empty(lib.fn('dis_colsum_bf16_workspace')(c_real), dtype=torch.float32, device=G.device)
-    lib.call('dis_colsum_bf16', G, _ld(G), 0, npix, c_real, out, ws)
-    return out
+def _convg_wgrad(*a):
+    _wgrad('dis_convg_wgrad', *a)
 
 
-class _ConvB(torch.autograd.Function):
-    """_ConvG with bf16 activation storage: x fp32 (the network input) or bf16, y bf16 (or a slot of a bf16 ConcatBuf)."""
+def _convb_wgrad(*a):
+    _wgrad('dis_convb_wgrad', *a)
 
+
+def _act_bwd_f32(gy, y, act, gb):
+    """Pre-activation gradient gpre = gy * act'(y) (dense fp32) of an nhwc gy; gy / y may be channel ranges of wider buffers (the
+    gradient of a concatenation, an output written into one).  gb: where the bias gradient goes if one pass over gy can give both
+    (None: not wanted).  -> (gpre, bias gradient written)"""
+    n, h, w, c = gy.shape
+    gpre = torch.empty(gy.shape, dtype=torch.float32, device=gy.device)
+    ldy = _ld(y) if y is not None else 0
+    if gb is not None and c <= 1024 and 256 % (c // 4) == 0 and gy.data_ptr() % 16 == 0 and (y is None or y.data_ptr() % 16 == 0):
+        ws = torch.empty(lib.fn('dis_act_bwd_ld_bias_workspace')(c), dtype=torch.float32, device=gy.device)
+        lib.call('dis_act_bwd_ld_bias', gy, _ld(gy), y, ldy, gpre, act, n * h * w, c, gb, ws)
+        return gpre, True
+    if gy.is_contiguous() and (y is None or y.is_contiguous()):
+        lib.call('dis_act_bwd', gy, y, gpre, act, gy.numel())
+    else:
+        lib.call('dis_act_bwd_ld', gy, _ld(gy), y, ldy, gpre, act, n * h * w, c)
+    return gpre, False
+
+
+def _act_bwd_bf16(gy, y, act, gb):
+    """_act_bwd_f32 on bf16 tensors (gpre bf16; the bias gradient is summed before gpre is rounded)"""
+    n, h, w, c = gy.shape
+    gpre = torch.empty(gy.shape, dtype=BF16, device=gy.device)
+    ldy = _ld(y) if y is not None else 0
+    if gb is not None and c <= 1024 and 256 % (c // 4) == 0:
+        ws = torch.empty(lib.fn('dis_colsum_bf16_workspace')(c), dtype=torch.float32, device=gy.device)
+        lib.call('dis_act_bwd_bf16_bias', gy, _ld(gy), y, ldy, gpre, act, n * h * w, c, gb, ws)
+        return gpre, True
+    lib.call('dis_act_bwd_bf16', gy, _ld(gy), y, ldy, gpre, act, n * h * w, c)
+    return gpre, False
+
+
+class _Storage(object):
+    """What differs between the two activation storages: dtype and channel multiple (16-byte vectors) of the feature maps, the check
+    of an input tensor, the forward-like launcher, the weight gradient, the entry points of the column sums and the channel copy (the
+    bf16 one also takes its source's storage flag), and the pre-activation gradient."""
+
+    def __init__(self, dtype, cmult, check, run, wgrad, colsum, copy, act_bwd):
+        self.dtype, self.cmult, self.check, self.run, self.wgrad = dtype, cmult, check, run, wgrad
+        self.colsum, self.copy, self.act_bwd = colsum, copy, act_bwd
+
+
+_F32 = _Storage(torch.float32, 4, _chk_f32, _convg_run, _convg_wgrad, 'dis_colsum', 'dis_copy_channels', _act_bwd_f32)
+_B16 = _Storage(BF16, 8, _chk_act, _convb_run, _convb_wgrad, 'dis_colsum_bf16', 'dis_copy_channels_bf16', _act_bwd_bf16)
+_STORAGE = {torch.float32: _F32, BF16: _B16}
+
+
+class _WriteChannels(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, pad, act, transposed, out_hw, need_dgrad, out=None):
-        x, weight = _nhwc(x), _c(weight)
-        _chk(weight, bias)
-        _chk_act(x)
-        n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y = _conv_stream_shapes(
-            'convb', x, weight, stride, pad, transposed, out_hw, out, BF16, 8)
-        _convb_run(CONVG_TCONV if transposed else CONVG_CONV, x, weight, bias, y, n, hin, win, cin_mem, cin_w, hout, wout,
-                   cout, cout, k, stride, pad, act)
-        ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
-        ctx.bias_ref = bias  # (gradient sink lookup)
-        ctx.cfg = (stride, pad, act, transposed, bias is not None, need_dgrad)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, weight, y = ctx.saved_tensors
-        stride, pad, act, transposed, has_bias, need_dgrad = ctx.cfg
-        n, hin, win, cin_mem = x.shape
-        gy = _nhwc(gy)
-        _, hout, wout, cout = gy.shape
-        k = weight.shape[2]
-        cin_w = weight.shape[0] if transposed else weight.shape[1]
-        if x.dtype == torch.float32 and not transposed and not (need_dgrad and ctx.needs_input_grad[0]) and x.is_contiguous():
-            # the network's first layer (fp32 input, no input gradient): fp32 pre-activation gradient and the one-pass fp32
-            # weight-gradient kernel of conv2d.hip (x and gy read once for all taps, bias gradient from the same pass)
-            wsz = lib.fn('dis_conv2d_wgrad_workspace')(cin_mem, cout, k, stride)
-            if wsz >= 0:
-                gpre = torch.empty(gy.shape, dtype=torch.float32, device=gy.device)
-                lib.call('dis_act_bwd_bf16_f32', gy, _ld(gy), y, _ld(y) if y is not None else 0, gpre, act, n * hout * wout,
-                         cout)
-                gw, gw_ret = _sink(weight)
-                ws = torch.empty(wsz, dtype=torch.float32, device=x.device)
-                gb, gb_ret = _sink_opt(ctx.bias_ref)
-                _conv_wgrad_any(x, gpre, gw, gb, ws, n, hin, win, cin_mem, cin_w, cout, k, stride, pad)
-                _sinks_written()
-                return None, gw_ret, gb_ret, None, None, None, None, None, None, None
-        gb, gb_ret = _sink_opt(ctx.bias_ref)
-        gb_done = False
-        if act != ACT_NONE or not gy.is_contiguous():
-            gpre = torch.empty(gy.shape, dtype=BF16, device=gy.device)
-            if has_bias and cout <= 1024 and 256 % (cout // 4) == 0:   # bias gradient from the same pass over gy
-                gb_done = True
-                ws = torch.empty(lib.fn('dis_colsum_bf16_workspace')(cout), dtype=torch.float32, device=gy.device)
-                lib.call('dis_act_bwd_bf16_bias', gy, _ld(gy), y, _ld(y) if y is not None else 0, gpre, act,
-                         n * hout * wout, cout, gb, ws)
-            else:
-                lib.call('dis_act_bwd_bf16', gy, _ld(gy), y, _ld(y) if y is not None else 0, gpre, act, n * hout * wout,
-                         cout)
-        else:
-            gpre = gy
-        gx = None
-        if need_dgrad and ctx.needs_input_grad[0]:
-            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-            _convb_run(CONVG_TCONV_DGRAD if transposed else CONVG_CONV_DGRAD, gpre, weight, None, gx, n, hout, wout, cout,
-                       cout, hin, win, cin_mem, cin_w, k, stride, pad, ACT_NONE)
-        gw, gw_ret = _sink(weight)
-        if transposed:
-            _convb_wgrad(gpre, hout, wout, cout, cout, x, hin, win, cin_mem, cin_w, gw, n, k, stride, pad)
-        else:
-            _convb_wgrad(x, hin, win, cin_mem, cin_w, gpre, hout, wout, cout, cout, gw, n, k, stride, pad)
-        if has_bias and not gb_done:
-            _colsum_b(gpre, cout, out=gb)
-        _sinks_written()
-        return gx, gw_ret, gb_ret, None, None, None, None, None, None, None
-
-
-class _HeadB(torch.autograd.Function):
-    """_HeadG on a bf16 feature map: Conv2d(cin,1,3,pad 1) + alpha*sigmoid(. - offset); the disparity is float32."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, alpha, offset):
-        x, weight, bias = _c(x), _c(weight), _c(bias)
-        _chk(weight, bias)
-        _chk_act(x)
-        return _head_stream_fwd(ctx, _convb_run, x, weight, bias, alpha, offset)
-
-    @staticmethod
-    def backward(ctx, gy):
-        return _head_stream_bwd(ctx, _convb_run, _convb_wgrad, gy)
-
-
-class _WriteChannelsB(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, src, slot, zero_tail):
+    def forward(ctx, st, src, slot, zero_tail):
         buf, off, c = slot
         n, h, w, cs = src.shape
-        assert cs == c and tuple(buf.shape[:3]) == (n, h, w) and buf.dtype == BF16
+        assert cs == c and tuple(buf.shape[:3]) == (n, h, w)
         src = _nhwc(src)
-        _chk_act(src) if src.dtype == BF16 else None
+        st.check(src)
         dst = buf[..., off:off + c]
-        lib.call('dis_copy_channels_bf16', src, _isbf(src), src.stride(2), dst, buf.shape[3], n * h * w, c,
+        lib.call(st.copy, src, *((_isbf(src),) if st is _B16 else ()), _ld(src), dst, buf.shape[3], n * h * w, c,
                  buf.shape[3] - off - c if zero_tail else 0)
         ctx.src_dtype = src.dtype
         return dst
 
     @staticmethod
     def backward(ctx, g):
-        return (g if ctx.src_dtype == BF16 else g.float()), None, None
+        return None, (g if g.dtype == ctx.src_dtype else g.float()), None, None   # (an fp32 source of a bf16 buffer)
+
+
+def write_channels(src, slot, zero_tail=False):
+    """copy the nhwc tensor src into a ConcatBuf slot; returns the slot's view (differentiable).  zero_tail: also zero the
+    buffer's padding lanes behind the slot (the slot must be the concatenation's last part)."""
+    return _WriteChannels.apply(_STORAGE[slot[0].dtype], src, slot, zero_tail)
+
+
+def _colsum(G, c_real, out=None):
+    """sum over all pixels of the first c_real channels of an nhwc tensor, fp32 or bf16 (into `out` if given)"""
+    entry = _STORAGE[G.dtype].colsum
+    npix = G.shape[0] * G.shape[1] * G.shape[2]
+    if out is None:
+        out = torch.empty(c_real, dtype=torch.float32, device=G.device)
+    ws = torch.empty(lib.fn(entry + '_workspace')(c_real), dtype=torch.float32, device=G.device)
+    lib.call(entry, G, _ld(G), 0, npix, c_real, out, ws)
+    return out
+
+
+def _conv_stream_shapes(st, x, weight, stride, pad, transposed, out_hw, out):
+    """Shapes of a _ConvStream forward and its output y in the storage st: a new tensor, or the ConcatBuf slot `out` = (buffer, channel
+    offset, channels).  -> (n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y)"""
+    n, hin, win, cin_mem = x.shape
+    if transposed:
+        cin_w, cout, k, _ = weight.shape
+        hout, wout = out_hw
+        if stride != 2 or hout > 2 * hin or wout > 2 * win:
+            raise RuntimeError('transposed conv: stride 2 and out_hw <= 2x input expected')
+    else:
+        cout, cin_w, k, _ = weight.shape
+        hout, wout = (hin + 2 * pad - k) // stride + 1, (win + 2 * pad - k) // stride + 1
+    fp32 = st is _F32   # (bf16 storage: _chk_act has checked x; its buffers are told apart from fp32 ones by dtype)
+    if (fp32 and cin_mem % 4) or cin_w > cin_mem or cout % st.cmult:
+        raise RuntimeError(f'streaming conv: bad channel counts cin_mem={cin_mem} cin_w={cin_w} cout={cout}')
+    if out is None:
+        y = torch.empty((n, hout, wout, cout), dtype=st.dtype, device=x.device)
+    else:
+        buf, off, c = out
+        if c != cout or tuple(buf.shape[:3]) != (n, hout, wout) or (not fp32 and buf.dtype != st.dtype):
+            raise RuntimeError(f'streaming conv: out slot {tuple(buf.shape)}[{off}:{off + c}] does not fit ({n},{hout},{wout},{cout})')
+        y = buf[..., off:off + c]
+    return n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y
+
+
+class _ConvStream(torch.autograd.Function):
+    """Conv2d / ConvTranspose2d(k,s2,p,op=1, cropped to out_hw) + bias + activation on nhwc tensors in the storage st.
+    x (n,h,w,cin_mem): cin_mem % 4 == 0 and >= the weight's input channels (extra channels must be zero-weight padding lanes; their
+    gradient is returned as zeros); in the bf16 storage x is bf16, or fp32 for the network input, and y is bf16."""
+
+    @staticmethod
+    def forward(ctx, st, x, weight, bias, stride, pad, act, transposed, out_hw, need_dgrad, out=None):
+        x, weight = _nhwc(x), _c(weight)  # (x may be a channel range of a ConcatBuf)
+        _chk(weight, bias)
+        st.check(x)
+        n, hin, win, cin_mem, cin_w, cout, k, hout, wout, y = _conv_stream_shapes(st, x, weight, stride, pad, transposed, out_hw, out)
+        st.run(CONVG_TCONV if transposed else CONVG_CONV, x, weight, bias, y, n, hin, win, cin_mem, cin_w, hout, wout, cout, cout,
+               k, stride, pad, act)
+        ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
+        ctx.bias_ref = bias  # (gradient sink lookup)
+        ctx.cfg = (st, stride, pad, act, transposed, bias is not None, need_dgrad)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight, y = ctx.saved_tensors
+        st, stride, pad, act, transposed, has_bias, need_dgrad = ctx.cfg
+        n, hin, win, cin_mem = x.shape
+        gy = _nhwc(gy)
+        _, hout, wout, cout = gy.shape
+        k = weight.shape[2]
+        cin_w = weight.shape[0] if transposed else weight.shape[1]
+        want_gx = need_dgrad and ctx.needs_input_grad[1]
+        # Shapes whose whole (tap, cin) x cout accumulator fits a workgroup's registers go through the one-pass fp32 kernels of
+        # conv2d.hip: x and gy are read once instead of once per tap, and the bias gradient comes out of the same pass.  In the bf16
+        # storage that is the network's first layer only: an fp32 x, no input gradient.
+        onepass = (not transposed and x.is_contiguous() and x.dtype == torch.float32 and (st is _F32 or not want_gx)
+                   and lib.fn('dis_conv2d_wgrad_workspace')(cin_mem, cout, k, stride) >= 0)
+        gb, gb_ret = _sink_opt(ctx.bias_ref)
+        gb_done = False
+        if onepass and st is _B16:   # the one-pass kernel takes an fp32 pre-activation gradient
+            gpre = torch.empty(gy.shape, dtype=torch.float32, device=gy.device)
+            lib.call('dis_act_bwd_bf16_f32', gy, _ld(gy), y, _ld(y) if y is not None else 0, gpre, act, n * hout * wout, cout)
+        elif act != ACT_NONE or not gy.is_contiguous():
+            gpre, gb_done = st.act_bwd(gy, y, act, None if onepass else gb)
+        else:
+            gpre = gy
+        gx = None
+        if want_gx:
+            gx = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+            st.run(CONVG_TCONV_DGRAD if transposed else CONVG_CONV_DGRAD, gpre, weight, None, gx, n, hout, wout, cout, cout, hin, win,
+                   cin_mem, cin_w, k, stride, pad, ACT_NONE)
+        gw, gw_ret = _sink(weight)
+        if onepass:
+            ws = torch.empty(lib.fn('dis_conv2d_wgrad_workspace')(cin_mem, cout, k, stride), dtype=torch.float32, device=x.device)
+            _conv_wgrad_any(x, gpre, gw, gb, ws, n, hin, win, cin_mem, cin_w, cout, k, stride, pad)
+        else:
+            if transposed:
+                st.wgrad(gpre, hout, wout, cout, cout, x, hin, win, cin_mem, cin_w, gw, n, k, stride, pad)
+            else:
+                st.wgrad(x, hin, win, cin_mem, cin_w, gpre, hout, wout, cout, cout, gw, n, k, stride, pad)
+            if has_bias and not gb_done:
+                _colsum(gpre, cout, out=gb)
+        _sinks_written()
+        return None, gx, gw_ret, gb_ret, None, None, None, None, None, None, None
+
+
+def convg(x, weight, bias, stride=1, pad=0, act=ACT_NONE, need_dgrad=True, out=None, dtype=torch.float32):
+    """Conv2d on an nhwc tensor through the streaming MFMA kernel (any channel count that is a multiple of 4).
+    out: optional ConcatBuf.slot the result is written into (the returned tensor is that channel range).
+    dtype=torch.bfloat16: bf16 activation storage (the result is bf16; x bf16, or fp32 for the network input)."""
+    return _ConvStream.apply(_STORAGE[dtype], x, weight, bias, stride, pad, act, False, None, need_dgrad, out)
+
+
+def convg_transposed(x, weight, bias, out_hw, pad=1, act=ACT_NONE, out=None, dtype=torch.float32):
+    """ConvTranspose2d(k=3, stride=2, padding=pad, output_padding=1) cropped to out_hw (crop_like)."""
+    return _ConvStream.apply(_STORAGE[dtype], x, weight, bias, 2, pad, act, True, tuple(out_hw), True, out)
+
+
+def _head_stream_fwd(ctx, st, x, weight, bias, alpha, offset):
+    """A disparity head as a one-channel streaming conv + alpha*sigmoid(. - offset); y is float32"""
+    n, h, w, cin = x.shape
+    k = weight.shape[2]
+    y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+    st.run(CONVG_CONV, x, weight, bias, y.view(n, h, w, 1), n, h, w, cin, weight.shape[1], h, w, 1, 1, k, 1, k // 2, ACT_NONE)
+    lib.call('dis_sigmoid_affine_fwd', y, y, float(alpha), float(offset), y.numel())
+    ctx.save_for_backward(x, weight, y)
+    ctx.alpha = float(alpha)
+    ctx.bias_ref = bias
+    return y
+
+
+def _head_stream_bwd(ctx, st, gy):
+    x, weight, y = ctx.saved_tensors
+    n, h, w, cin = x.shape
+    k = weight.shape[2]
+    cin_w = weight.shape[1]
+    gpre4 = torch.empty((n, h, w, 4), dtype=torch.float32, device=x.device)
+    lib.call('dis_sigmoid_affine_bwd', y, _c(gy), gpre4, ctx.alpha, n * h * w)
+    gx = torch.empty_like(x)
+    st.run(CONVG_CONV_DGRAD, gpre4, weight, None, gx, n, h, w, 4, 1, h, w, cin, cin_w, k, 1, k // 2, ACT_NONE)
+    gw, gw_ret = _sink(weight)
+    gb, gb_ret = _sink(ctx.bias_ref)
+    st.wgrad(x, h, w, cin, cin_w, gpre4, h, w, 4, 1, gw, n, k, 1, k // 2)
+    _colsum(gpre4, 1, out=gb)
+    _sinks_written()
+    return None, gx, gw_ret, gb_ret, None, None
+
+
+class _HeadStream(torch.autograd.Function):
+    """Conv2d(cin,1,3,pad 1) + alpha*sigmoid(. - offset): x nhwc in the storage st (fp32: any cin % 4 == 0) -> y planar (n,1,h,w),
+    float32."""
+
+    @staticmethod
+    def forward(ctx, st, x, weight, bias, alpha, offset):
+        x, weight, bias = _c(x), _c(weight), _c(bias)
+        _chk(weight, bias)
+        st.check(x)
+        n, h, w, cin = x.shape
+        ctx.st = st
+        # the one-pass head kernels (fp32 x, 16 / 32 channels)
+        ctx.direct = st is _F32 and weight.shape[2] == 3 and cin in (16, 32) and weight.shape[1] == cin
+        if ctx.direct:
+            y = torch.empty((n, 1, h, w), dtype=torch.float32, device=x.device)
+            lib.call('dis_disp_head_fwd', x, weight, bias, y, n, h, w, cin, float(alpha), float(offset))
+            ctx.save_for_backward(x, weight, y)
+            ctx.alpha = float(alpha)
+            ctx.bias_ref = bias
+            return y
+        return _head_stream_fwd(ctx, st, x, weight, bias, alpha, offset)
+
+    @staticmethod
+    def backward(ctx, gy):
+        if not ctx.direct:
+            return _head_stream_bwd(ctx, ctx.st, gy)
+        x, weight, y = ctx.saved_tensors
+        n, h, w, cin = x.shape
+        gw, gw_ret = _sink(weight)
+        gb, gb_ret = _sink(ctx.bias_ref)
+        gx = torch.empty_like(x)
+        ws = torch.empty(lib.fn('dis_disp_head_bwd_workspace')(n, h, w, cin), dtype=torch.float32, device=x.device)
+        lib.call('dis_disp_head_bwd', x, weight, y, _c(gy), gx, gw, gb, ws, n, h, w, cin, ctx.alpha)
+        _sinks_written()
+        return None, gx, gw_ret, gb_ret, None, None
+
+
+def disp_head_g(x, weight, bias, alpha, offset=3.0):
+    return _HeadStream.apply(_STORAGE[x.dtype], x, weight, bias, alpha, offset)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -31,7 +31,8 @@ HALO = 'bf16 LDS halo)'
 HALO_KC = 'column walk'
 HALO_4PH = '4 phases'
 PAIRS = 'conv_wgrad_bf16x3_kernel<BF> slice pairs'
-NO_TAG = ''   # convb_wgrad_kernel and convb_head_wgrad_kernel report no tag: "not the slice-pair form"
+WGRAD_GENERIC = 'stream_wgrad_kernel (fp32 MFMA, split-K slabs)'     # conv_stream_wgrad.hip, for fp32 and bf16 operands alike
+WGRAD_HEAD = 'stream_head_wgrad_kernel (one gradient channel)'
 
 # fwd / dgrad: substring every dis_convb_run launch tag of the forward / input-gradient call must contain (dgrad None: not pinned;
 # for a phased call the recorder keeps the LAST phase's tag).  wgrad: the exact tag of the dis_convb_wgrad call; None: the layer has
@@ -50,12 +51,12 @@ CASES = [
     _c('stream_k5s2', 32, 32, 64, 5, 2, 21, 19, True, STREAM, STREAM, PAIRS),                 # odd sizes; pairs k5 s2
     _c('stream_k5', 64, 64, 64, 5, 1, 11, 13, False, STREAM, STREAM, PAIRS),                  # pairs k5 s1
     _c('stream_17in24_16', 17, 24, 16, 3, 1, 16, 12, True, STREAM, STREAM, PAIRS),            # 16-wide cout block; pairs k3 s1, 16 outputs
-    _c('stream_32_24', 32, 32, 24, 3, 1, 9, 13, False, STREAM, STREAM, NO_TAG),               # partial 32-wide block; generic wgrad (24 outputs)
+    _c('stream_32_24', 32, 32, 24, 3, 1, 9, 13, False, STREAM, STREAM, WGRAD_GENERIC),               # partial 32-wide block; generic wgrad (24 outputs)
     _c('stream_64_72', 64, 64, 72, 3, 1, 9, 13, True, STREAM, STREAM, PAIRS),                 # second 64-wide block holds 8 channels
     _c('stream_128_16', 128, 128, 16, 3, 1, 9, 7, False, STREAM, STREAM, PAIRS),              # cin >= 128 but a 16-wide cout block
     _c('stream_tiny', 32, 32, 32, 3, 1, 3, 2, True, STREAM, STREAM, PAIRS, n=3),              # 18 positions in all: one ragged tile
-    _c('stream_8_32', 8, 8, 32, 3, 1, 13, 11, True, STREAM, STREAM, NO_TAG),                  # generic wgrad (< 16 input channels)
-    _c('stream_k7s2_bf16', 32, 32, 32, 7, 2, 21, 19, False, STREAM, STREAM, NO_TAG),          # generic wgrad (k7 s2 has no pair instance)
+    _c('stream_8_32', 8, 8, 32, 3, 1, 13, 11, True, STREAM, STREAM, WGRAD_GENERIC),                  # generic wgrad (< 16 input channels)
+    _c('stream_k7s2_bf16', 32, 32, 32, 7, 2, 21, 19, False, STREAM, STREAM, WGRAD_GENERIC),          # generic wgrad (k7 s2 has no pair instance)
     _c('stream_tconv_crop', 64, 64, 32, 3, 2, 8, 7, True, STREAM, STREAM, PAIRS, transposed=True, crop=True),    # 15 x 13 of 16 x 14
     _c('stream_tconv_full', 64, 64, 32, 3, 2, 8, 7, False, STREAM, STREAM, PAIRS, transposed=True),              # pairs k3 s2, x / gy swapped
     # ---- 128-channel stages: cin >= 128, bf16 x, < 1024 positions ----

@@ -141,14 +141,14 @@ def test_convb_partial_cout_block(cin, cout, ldy, relu):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the bf16 disparity head (ops._HeadB): its three convolution pieces on their own, exactly
+# the bf16 disparity head (ops._HeadStream on a bf16 x): its three convolution pieces on their own, exactly
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('cin,h,w', [(16, 13, 17), (32, 13, 17), (64, 13, 17), (128, 13, 17), (24, 13, 17), (64, 32, 33)])
 def test_convb_head_pieces_equal_fp64_on_integers(cin, h, w):
     """ops._convb_run / ops._convb_wgrad called exactly as _head_stream_fwd / _head_stream_bwd call them: the one-channel fp32
     pre-activation, the input gradient from a 4-lane fp32 buffer with one real channel, and the head weight gradient
-    (convb_head_wgrad_kernel for cin in {16, 32, 64, 128}; cin = 24 is not eligible (cbh_eligible) and runs the generic
-    convb_wgrad_kernel with a bf16 x and an fp32 gradient).  32 x 33 = 1056 positions: the halo form with an fp32 y / an fp32 x."""
+    (stream_head_wgrad_kernel for cin in {16, 32, 64, 128}; cin = 24 has no head instance and runs the generic
+    stream_wgrad_kernel with a bf16 x and an fp32 gradient).  32 x 33 = 1056 positions: the halo form with an fp32 y / an fp32 x."""
     from depthinspace_amd import ops
     g = torch.Generator().manual_seed(cin + h)
     n, k = 2, 3
@@ -182,17 +182,18 @@ def test_convb_head_pieces_equal_fp64_on_integers(cin, h, w):
     # weight gradient
     gw = torch.full((1, cin, k, k), 9.0, dtype=torch.float32, device='cuda')
     _, rec = _recorded(lambda: ops._convb_wgrad(xd, h, w, cin, cin, gpre4, h, w, 4, 1, gw, n, k, 1, k // 2))
-    assert rec == [('dis_convb_wgrad', R.NO_TAG)], rec     # (an fp32 gradient never takes the slice-pair form)
+    tag = R.WGRAD_HEAD if cin in (16, 32, 64, 128) else R.WGRAD_GENERIC    # (an fp32 gradient never takes the slice-pair form)
+    assert rec == [('dis_convb_wgrad', tag)], rec
     msg = _diff('gw', gw, wt.grad)
     assert msg is None, msg
 
 
 @pytest.mark.parametrize('cin,alpha', [(128, 16.0), (64, 32.0), (32, 64.0), (16, 128.0)])
 def test_disp_head_g_bf16_vs_fp64(cin, alpha):
-    """ops.disp_head_g on a bf16 feature map (ops._HeadB) against float64, the shapes of test_convg_head_fwd_bwd.  Operands that
+    """ops.disp_head_g on a bf16 feature map (ops._HeadStream) against float64, the shapes of test_convg_head_fwd_bwd.  Operands that
     are exact in bf16 (integers x, multiples of 1/16 in the weights), so that the pre-activation is exact and only the sigmoid's
     fp32 evaluation separates y from float64: the fp32 twin's bar, 2e-5 of the largest entry.
-    Gradients.  gw, gb: x is exact, the pre-activation gradient stays fp32 (convb_head_wgrad_kernel reads it unrounded), fp32
+    Gradients.  gw, gb: x is exact, the pre-activation gradient stays fp32 (stream_head_wgrad_kernel reads it unrounded), fp32
     sums: the fp32 twin's 5e-5 of the largest entry.  gx is a bf16 tensor computed from the fp32 pre-activation gradient, which the
     kernel rounds to bf16 when it stages it: element by element
         |gx - ref| <= 2^-8 * convT(|gpre|, |w|)     (each gpre rounded to nearest, 8 significant bits: unit roundoff 2^-8)

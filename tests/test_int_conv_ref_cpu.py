@@ -23,7 +23,7 @@ def test_table_is_well_formed():
         m = R.m_of(c.cin_w, c.k)
         assert c.k * c.k * m * 2 * 2 + 8 <= R.BOUND, c.id
     tags = {c.fwd for c in R.CASES} | {c.dgrad for c in R.CASES} | {c.wgrad for c in R.CASES}
-    for t in (R.STREAM, R.ST128, R.SPLITK, R.BIG, R.HALO, R.HALO_KC, R.HALO_4PH, R.PAIRS, R.NO_TAG):
+    for t in (R.STREAM, R.ST128, R.SPLITK, R.BIG, R.HALO, R.HALO_KC, R.HALO_4PH, R.PAIRS, R.WGRAD_GENERIC):
         assert t in tags, t
 
 
