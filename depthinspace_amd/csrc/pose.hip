@@ -15,35 +15,15 @@
 // workspace needs no initialisation.
 // The second half of the file is the joint refinement, dis_refine_track_poses: one pose per frame on the residuals of all pairs at once,
 // through the same per-pixel function (pose_pixel) and the same reduction (pose_block_record).
+// The reduction, the record sum and the 6 x 6 step (pose_hidx, pose_add_row, pose_block_record, pose_sum_records, pose_gn_step,
+// pose_apply_twist) live in track_common.h: tsdf_align.hip runs its own per-pixel terms through them.
 #include "track_common.h"
-
-#define POSE_BLOCK 256
-#define POSE_WAVES (POSE_BLOCK / DIS_WAVE)
-#define POSE_SUMS 30     // H_pq (p <= q, row by row) 0 .. 20, g_p 21 .. 26, S_w 27, S_c 28, n 29
-#define POSE_REC 32      // doubles per record of partial sums
-#define POSE_STATE 16    // doubles per pair: R (9, row-major), t (3), failed (1), 3 unused
-#define POSE_MAX_BPP 128
-#define POSE_BATCH 32    // records in flight per lane of the solve launch
 
 struct PoseParams {
   int n, tl, h, w, hw, bpp;              // bpp = workgroups per pair
   TrackCamera cam;
   float s2;                              // scale * scale
 };
-
-__device__ __forceinline__ constexpr int pose_hidx(int p, int q) { return p * 6 - p * (p - 1) / 2 + (q - p); }
-
-// the terms of one residual row: J[] at the indices idx[0 .. m) (the other entries are structurally zero and are skipped)
-template <int M>
-__device__ __forceinline__ void pose_add_row(double* acc, const float wgt, const float* J, const int (&idx)[M], const float e) {
-#pragma unroll
-  for (int a = 0; a < M; ++a) {
-    const float wJ = wgt * J[a];
-#pragma unroll
-    for (int b = a; b < M; ++b) acc[pose_hidx(idx[a], idx[b])] += (double)(wJ * J[b]);
-    acc[21 + idx[a]] += (double)(wJ * e);
-  }
-}
 
 // One pixel of the pair (i, j) at the state (R, t): its target in frame j (its disparity, its flow, four gathered disparities of frame j),
 // the 30 terms at the state's fp32 rounding, added to acc[] in fp64.  A pixel that is not matched or not used adds nothing.  The one
@@ -91,23 +71,6 @@ __device__ __forceinline__ void pose_pixel(double* acc, const float* __restrict_
   acc[29] += 1.0;
 }
 
-// every lane of the workgroup calls (a barrier is passed): the sum of acc[] over the wave, over the four waves through LDS -> rec[0 .. 32)
-__device__ __forceinline__ void pose_block_record(const double* acc, double* __restrict__ rec) {
-  __shared__ double wave_part[POSE_WAVES][POSE_REC];
-  const int lane = threadIdx.x & (DIS_WAVE - 1), wid = threadIdx.x / DIS_WAVE;
-#pragma unroll
-  for (int k = 0; k < POSE_SUMS; ++k) {
-    const double s = wave_sum_d(acc[k]);           // valid in every lane
-    if (lane == 0) wave_part[wid][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < POSE_REC) {
-    double s = 0.0;
-    if (threadIdx.x < POSE_SUMS) s = (wave_part[0][threadIdx.x] + wave_part[1][threadIdx.x]) + (wave_part[2][threadIdx.x] + wave_part[3][threadIdx.x]);
-    rec[threadIdx.x] = s;
-  }
-}
-
 __global__ __launch_bounds__(POSE_BLOCK) void pose_accum_kernel(const float* __restrict__ disp, const float* __restrict__ flow,
                                                                 const double* __restrict__ state, double* __restrict__ partial,
                                                                 const PoseParams p, const int first) {
@@ -131,7 +94,7 @@ __global__ __launch_bounds__(POSE_BLOCK) void pose_accum_kernel(const float* __r
 #pragma unroll
   for (int k = 0; k < POSE_SUMS; ++k) acc[k] = 0.0;
   for (int pix = blk * POSE_BLOCK + (int)threadIdx.x; pix < p.hw; pix += p.bpp * POSE_BLOCK) pose_pixel(acc, di, dj, fl, pix, p, R, t, first);
-  pose_block_record(acc, partial + ((size_t)pair * p.bpp + blk) * POSE_REC);
+  pose_block_record<POSE_SUMS>(acc, partial + ((size_t)pair * p.bpp + blk) * POSE_REC);
 }
 
 struct PoseSolveParams {
@@ -157,20 +120,7 @@ __global__ __launch_bounds__(DIS_WAVE) void pose_solve_kernel(const double* __re
     }
     return;
   }
-  if (threadIdx.x < POSE_SUMS) {
-    // ascending workgroup order; the records are asked for POSE_BATCH at a time, so that the additions do not wait for one load each
-    const double* rec = partial + (size_t)pair * p.bpp * POSE_REC + threadIdx.x;
-    double s = 0.0;
-    for (int k = 0; k < p.bpp; k += POSE_BATCH) {
-      double v[POSE_BATCH];
-#pragma unroll
-      for (int m = 0; m < POSE_BATCH; ++m) v[m] = rec[(size_t)min(k + m, p.bpp - 1) * POSE_REC];
-#pragma unroll
-      for (int m = 0; m < POSE_BATCH; ++m)
-        if (k + m < p.bpp) s += v[m];
-    }
-    S[threadIdx.x] = s;
-  }
+  if (threadIdx.x < POSE_SUMS) S[threadIdx.x] = pose_sum_records(partial + (size_t)pair * p.bpp * POSE_REC + threadIdx.x, p.bpp);
   __syncthreads();
   if (threadIdx.x != 0) return;
   double* st = state + (size_t)pair * POSE_STATE;
@@ -195,73 +145,7 @@ __global__ __launch_bounds__(DIS_WAVE) void pose_solve_kernel(const double* __re
     stats[(size_t)pair * 4 + 3] = failed ? 0.f : 1.f;
     return;
   }
-  if (!failed) {
-    failed = S[29] < (double)p.min_corr;
-    double L[6][6], d[6];
-    if (!failed) {
-      // Cholesky of H + damping diag(H), column by column; a pivot that is not > 0 or not finite ends the pair
-      // (a bad pivot lets the remaining columns run on: their values are not used)
-#pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        const double hcc = S[pose_hidx(c, c)];
-        double s = hcc + p.damping * hcc;
-#pragma unroll
-        for (int k = 0; k < c; ++k) s = s - L[c][k] * L[c][k];
-        if (!(s > 0.0 && s <= 1.7976931348623157e308)) failed = true;
-        L[c][c] = sqrt(s);
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-          double q = S[pose_hidx(c, r)];
-#pragma unroll
-          for (int k = 0; k < c; ++k) q = q - L[r][k] * L[c][k];
-          L[r][c] = q / L[c][c];
-        }
-      }
-    }
-    if (!failed) {
-      double y[6];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        double s = -S[21 + r];
-#pragma unroll
-        for (int k = 0; k < r; ++k) s = s - L[r][k] * y[k];
-        y[r] = s / L[r][r];
-      }
-#pragma unroll
-      for (int r = 5; r >= 0; --r) {
-        double s = y[r];
-#pragma unroll
-        for (int k = r + 1; k < 6; ++k) s = s - L[k][r] * d[k];
-        d[r] = s / L[r][r];
-      }
-      const double th2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
-      double ca = 1.0, cb = 0.5;
-      if (!(th2 < 1e-16)) {
-        const double th = sqrt(th2);
-        ca = sin(th) / th;
-        cb = (1.0 - cos(th)) / th2;
-      }
-      // dR = I + ca [w]x + cb [w]x^2, [w]x^2 = w w^T - th2 I
-      double dR[9];
-      const double Wx[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          dR[3 * r + c] = ((r == c ? 1.0 : 0.0) + ca * Wx[3 * r + c]) + cb * (d[r] * d[c] - (r == c ? th2 : 0.0));
-      double Rn[9], tn[3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Rn[3 * r + c] = (dR[3 * r] * R[c] + dR[3 * r + 1] * R[3 + c]) + dR[3 * r + 2] * R[6 + c];
-        tn[r] = ((dR[3 * r] * t[0] + dR[3 * r + 1] * t[1]) + dR[3 * r + 2] * t[2]) + d[3 + r];
-      }
-#pragma unroll
-      for (int k = 0; k < 9; ++k) R[k] = Rn[k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) t[k] = tn[k];
-    }
-  }
+  if (!failed) failed = !pose_gn_step(S, p.min_corr, p.damping, R, t);
 #pragma unroll
   for (int k = 0; k < 9; ++k) st[k] = R[k];
 #pragma unroll
@@ -280,9 +164,7 @@ static bool pose_plan(int n, int tl, int h, int w, PosePlan* pl) {
   if (n < 1 || tl < 2 || tl > TRACK_MAX_TL || !track_image_ok(h, w, 2)) return false;
   if ((long)n * tl * tl * 2 * h * w > 0x7fffffffL) return false;
   pl->pairs = (long)n * tl * tl;
-  int bpp = dis_cdiv((long)h * w, 4 * POSE_BLOCK);   // about four pixels per lane, until the cap
-  if (bpp > POSE_MAX_BPP) bpp = POSE_MAX_BPP;
-  pl->bpp = bpp;
+  const int bpp = pl->bpp = pose_bpp(h, w);
   TrackCarver ws = {16, 0};
   pl->off_state = ws.take(pl->pairs * POSE_STATE * 8);
   pl->off_partial = ws.take(pl->pairs * bpp * POSE_REC * 8);
@@ -409,7 +291,7 @@ __global__ __launch_bounds__(POSE_BLOCK) void pose_joint_accum_kernel(const floa
 #pragma unroll
   for (int k = 0; k < POSE_SUMS; ++k) acc[k] = 0.0;
   for (int pix = blk * POSE_BLOCK + (int)threadIdx.x; pix < p.hw; pix += p.bpp * POSE_BLOCK) pose_pixel(acc, di, dj, fl, pix, p, R, t, 0);
-  pose_block_record(acc, partial + ((size_t)pair * p.bpp + blk) * POSE_REC);
+  pose_block_record<POSE_SUMS>(acc, partial + ((size_t)pair * p.bpp + blk) * POSE_REC);
 }
 
 __global__ __launch_bounds__(POSEJ_BLOCK) void pose_joint_solve_kernel(const double* __restrict__ partial, const float* __restrict__ R_init,
@@ -433,18 +315,7 @@ __global__ __launch_bounds__(POSEJ_BLOCK) void pose_joint_solve_kernel(const dou
     const bool used = pr / tl != pr % tl && (!pair_use || pair_use[(size_t)b * tt + pr]);
     if (lane < POSE_REC) {
       double s = 0.0;
-      if (used && lane < POSE_SUMS) {
-        // ascending workgroup order; the records are asked for POSE_BATCH at a time, so that the additions do not wait for one load each
-        const double* rec = partial + ((size_t)b * tt + pr) * p.bpp * POSE_REC + lane;
-        for (int k = 0; k < p.bpp; k += POSE_BATCH) {
-          double v[POSE_BATCH];
-#pragma unroll
-          for (int q = 0; q < POSE_BATCH; ++q) v[q] = rec[(size_t)min(k + q, p.bpp - 1) * POSE_REC];
-#pragma unroll
-          for (int q = 0; q < POSE_BATCH; ++q)
-            if (k + q < p.bpp) s += v[q];
-        }
-      }
+      if (used && lane < POSE_SUMS) s = pose_sum_records(partial + ((size_t)b * tt + pr) * p.bpp * POSE_REC + lane, p.bpp);
       S[pr][lane] = s;
     }
   }
@@ -582,35 +453,7 @@ __global__ __launch_bounds__(POSEJ_BLOCK) void pose_joint_solve_kernel(const dou
     failed = failed_s != 0;
     if (!failed && tid >= 1 && tid < tl) {
       // the update of pose_solve_kernel, frame tid
-      const double* dd = dv + 6 * (tid - 1);
-      double* R = F[tid];
-      double* t = F[tid] + 9;
-      const double th2 = (dd[0] * dd[0] + dd[1] * dd[1]) + dd[2] * dd[2];
-      double ca = 1.0, cb = 0.5;
-      if (!(th2 < 1e-16)) {
-        const double th = sqrt(th2);
-        ca = sin(th) / th;
-        cb = (1.0 - cos(th)) / th2;
-      }
-      // dR = I + ca [w]x + cb [w]x^2, [w]x^2 = w w^T - th2 I
-      double dR[9];
-      const double Wx[9] = {0.0, -dd[2], dd[1], dd[2], 0.0, -dd[0], -dd[1], dd[0], 0.0};
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-          dR[3 * r + c] = ((r == c ? 1.0 : 0.0) + ca * Wx[3 * r + c]) + cb * (dd[r] * dd[c] - (r == c ? th2 : 0.0));
-      double Rn[9], tn[3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Rn[3 * r + c] = (dR[3 * r] * R[c] + dR[3 * r + 1] * R[3 + c]) + dR[3 * r + 2] * R[6 + c];
-        tn[r] = ((dR[3 * r] * t[0] + dR[3 * r + 1] * t[1]) + dR[3 * r + 2] * t[2]) + dd[3 + r];
-      }
-#pragma unroll
-      for (int k = 0; k < 9; ++k) R[k] = Rn[k];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) t[k] = tn[k];
+      pose_apply_twist(dv + 6 * (tid - 1), F[tid], F[tid] + 9);
     }
     __syncthreads();
   }

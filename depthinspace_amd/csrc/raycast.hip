@@ -21,6 +21,8 @@
 //                          on says whether n* - 1 is valid.
 //     Both variants end in the same code - s(n* - 1) and s(n*) gathered again, the crossing, the gradient, the value - so they give the
 //     same bits.
+// The cell rule and the sampler (ray_cell, ray_corners, ray_trilinear, ray_gradient, ray_weights_ok) live in track_common.h:
+// tsdf_align.hip samples the volume through them too.
 #include "track_common.h"
 
 #define RAY_BLOCK TRACK_BLOCK
@@ -93,12 +95,6 @@ __global__ __launch_bounds__(RAY_BLOCK) void raycast_brick_kernel(const unsigned
   track_block_count(cnt, brick);
 }
 
-struct RaySample {
-  bool inside;
-  int ix, iy, iz;
-  float fx, fy, fz;
-};
-
 struct Ray {
   float o0, o1, o2, d0, d1, d2;
 };
@@ -109,38 +105,7 @@ __device__ __forceinline__ RaySample ray_sample(int n, const Ray& q, const RayPa
   const float gx = ((q.o0 + z * q.d0) - p.ox) / p.voxel;
   const float gy = ((q.o1 + z * q.d1) - p.oy) / p.voxel;
   const float gz = ((q.o2 + z * q.d2) - p.oz) / p.voxel;
-  RaySample s;
-  s.inside = gx >= 0.f && gx < (float)(p.nx - 1) && gy >= 0.f && gy < (float)(p.ny - 1) && gz >= 0.f && gz < (float)(p.nz - 1);
-  s.ix = s.inside ? (int)floorf(gx) : 0;
-  s.iy = s.inside ? (int)floorf(gy) : 0;
-  s.iz = s.inside ? (int)floorf(gz) : 0;
-  s.fx = gx - (float)s.ix, s.fy = gy - (float)s.iy, s.fz = gz - (float)s.iz;
-  return s;
-}
-
-// the eight corners of the sample's cell, corner c at the offsets (c & 1, c >> 1 & 1, c >> 2)
-__device__ __forceinline__ void ray_corners(const float* __restrict__ A, const RaySample& s, const RayParams& p, float* c) {
-  const size_t l = ((size_t)s.iz * p.ny + s.iy) * p.nx + s.ix;
-  const int nxy = p.nx * p.ny;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) c[k] = A[l + (k & 1) + ((k >> 1) & 1) * p.nx + (k >> 2) * nxy];
-}
-
-// along x, then y, then z, each a + f (b - a)
-__device__ __forceinline__ float ray_trilinear(const float* c, const RaySample& s) {
-  const float c00 = c[0] + s.fx * (c[1] - c[0]), c10 = c[2] + s.fx * (c[3] - c[2]);
-  const float c01 = c[4] + s.fx * (c[5] - c[4]), c11 = c[6] + s.fx * (c[7] - c[6]);
-  const float c0 = c00 + s.fy * (c10 - c00), c1 = c01 + s.fy * (c11 - c01);
-  return c0 + s.fz * (c1 - c0);
-}
-
-__device__ __forceinline__ bool ray_weights_ok(const unsigned char* __restrict__ weight, const RaySample& s, const RayParams& p) {
-  const size_t l = ((size_t)s.iz * p.ny + s.iy) * p.nx + s.ix;
-  const int nxy = p.nx * p.ny;
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) ok = ok && (int)weight[l + (k & 1) + ((k >> 1) & 1) * p.nx + (k >> 2) * nxy] >= p.min_weight;
-  return ok;
+  return ray_cell(gx, gy, gz, p);
 }
 
 // [0, 2^24] as an int, whatever q is (NaN: 0)
@@ -276,12 +241,9 @@ __global__ __launch_bounds__(RAY_BLOCK) void raycast_march_kernel(const float* _
       const float zs = (float)(nstar - 1) * p.step + p.step * (s0 / (s0 - s1));
       od = p.cam.fb / zs;
       // the gradient of the trilinear interpolant at sample n*, in lattice units (the voxel cancels in the normalisation)
-      const float dx00 = c[1] - c[0], dx10 = c[3] - c[2], dx01 = c[5] - c[4], dx11 = c[7] - c[6];
-      const float c00 = c[0] + sb.fx * dx00, c10 = c[2] + sb.fx * dx10, c01 = c[4] + sb.fx * dx01, c11 = c[6] + sb.fx * dx11;
-      const float gx0 = dx00 + sb.fy * (dx10 - dx00), gx1 = dx01 + sb.fy * (dx11 - dx01);
-      const float dy0 = c10 - c00, dy1 = c11 - c01;
-      const float c0 = c00 + sb.fy * dy0, c1 = c01 + sb.fy * dy1;
-      const float g0 = gx0 + sb.fz * (gx1 - gx0), g1 = dy0 + sb.fz * (dy1 - dy0), g2 = c1 - c0;
+      float g[3];
+      ray_gradient(c, sb, g);
+      const float g0 = g[0], g1 = g[1], g2 = g[2];
       const float len = sqrtf((g0 * g0 + g1 * g1) + g2 * g2);
       if (track_pos_finite(len)) on0 = g0 / len, on1 = g1 / len, on2 = g2 / len;
       ray_corners(vvalue, sb, p, c);

@@ -56,27 +56,44 @@ def place_volume(points, res=256, voxel=None, trunc_voxels=3.0):
     return origin, voxel, trunc, grid
 
 
-def integrate_track(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3.0, tol=0.01, min_views=2, device='cuda'):
-    """one track, float32 numpy in: the volume placed around the points ops.fuse_track keeps (place_volume) and integrated by
-    ops.tsdf_integrate - what data/mesh.py and data/raycast.py share.  -> dict of the device tensors tsdf, weight, vvalue, R, t and
-    origin, voxel, trunc, grid, K - or None when fuse_track keeps no point or the box has no extent"""
-    from .. import ops
+def _upload(disp, R, t, value, device):
     dev = torch.device(device)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-    d_disp, d_R, d_t = up(disp), up(R), up(t)
-    d_val = None if value is None else up(value)
-    K = np.asarray(settings.K, dtype=np.float32)
-    r = ops.fuse_track(d_disp[None], d_R[None], d_t[None], K, settings.baseline, None if d_val is None else d_val[None], tol=tol,
-                       min_views=min_views)
+    return up(disp), up(R), up(t), None if value is None else up(value)
+
+
+def place_track(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3.0, tol=0.01, min_views=2, device='cuda'):
+    """one track, float32 numpy in: the lattice placed around the points ops.fuse_track keeps (place_volume) -> origin, voxel, trunc, grid
+    - or None when fuse_track keeps no point or the box has no extent.  The first half of integrate_track"""
+    from .. import ops
+    d_disp, d_R, d_t, d_val = _upload(disp, R, t, value, device)
+    r = ops.fuse_track(d_disp[None], d_R[None], d_t[None], np.asarray(settings.K, dtype=np.float32), settings.baseline,
+                       None if d_val is None else d_val[None], tol=tol, min_views=min_views)
     m = int(r['count'].sum().item())
     if m == 0:
         return None
-    place = place_volume(r['xyz'][:m], res, voxel, trunc_voxels)
-    if place is None:
-        return None
+    return place_volume(r['xyz'][:m], res, voxel, trunc_voxels)
+
+
+def integrate_placed(disp, R, t, value, settings, place, device='cuda'):
+    """one track (or some of its frames), float32 numpy in, integrated by ops.tsdf_integrate into the lattice `place` = origin, voxel,
+    trunc, grid of place_track: the second half of integrate_track.  -> its dict"""
+    from .. import ops
+    d_disp, d_R, d_t, d_val = _upload(disp, R, t, value, device)
+    K = np.asarray(settings.K, dtype=np.float32)
     origin, vx, trunc, grid = place
     tsdf, weight, vvalue = ops.tsdf_integrate(d_disp, d_R, d_t, K, settings.baseline, d_val, origin=origin, voxel=vx, trunc=trunc, grid=grid)
     return dict(tsdf=tsdf, weight=weight, vvalue=vvalue, R=d_R, t=d_t, origin=origin, voxel=vx, trunc=trunc, grid=grid, K=K)
+
+
+def integrate_track(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3.0, tol=0.01, min_views=2, device='cuda'):
+    """one track, float32 numpy in: the volume placed around the points ops.fuse_track keeps (place_track) and integrated by
+    ops.tsdf_integrate (integrate_placed) - what data/mesh.py and data/raycast.py share.  -> dict of the device tensors tsdf, weight,
+    vvalue, R, t and origin, voxel, trunc, grid, K - or None when fuse_track keeps no point or the box has no extent"""
+    place = place_track(disp, R, t, value, settings, res, voxel, trunc_voxels, tol, min_views, device)
+    if place is None:
+        return None
+    return integrate_placed(disp, R, t, value, settings, place, device)
 
 
 def mesh_arrays(disp, R, t, value, settings, res=256, voxel=None, trunc_voxels=3.0, min_weight=1, tol=0.01, min_views=2, device='cuda'):

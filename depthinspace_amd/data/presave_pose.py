@@ -12,6 +12,8 @@ whose pairs failed is listed as failed and left as it is.
 
     python -m depthinspace_amd.data.presave_pose ROOT [--disp gt|sgm|single_frame|multi_frame] [--iters N] [--scale S] [--damping D]
                                                       [--min-corr N] [--force] [--report] [--pack] [--joint] [--joint-iters N]
+                                                      [--model] [--model-rounds N] [--model-iters N] [--res N | --voxel V]
+                                                      [--trunc VOXELS] [--min-weight N] [--tol T] [--min-views N]
 
 A track that already stores R and t is skipped unless --force is given: rendered tracks keep their exact poses.  --report also
 estimates the tracks that are skipped and prints one line over the dataset: the pairs that are ok / failed, the mean share of the
@@ -30,6 +32,23 @@ written with its composed pairwise poses and counted (`joint_failed`); --report 
 pairs, their share of the ordered pairs, and against stored poses the errors of the joint poses (`joint_gt_rot`, `joint_gt_trans`,
 over all ordered pairs) next to the pairwise ones.  Still not done: the intrinsics are taken as given, there is no loop closure
 across tracks, no step control beyond the damping term, and a track has at most four frames.
+
+--model adds a last stage before the poses are written, after the pairwise estimate and, if given, --joint: frame-to-model refinement,
+the tracking step of KinectFusion (ops.tsdf_align_poses / dis_tsdf_align_poses).  The poses so far place one lattice around the track as
+data/mesh.py does (--res or --voxel, --trunc, --tol, --min-views); then, for --model-rounds rounds and each frame but the first, the
+other frames are integrated into that lattice at their current poses and the frame is aligned to the volume by --model-iters
+Gauss-Newton steps on the signed distance of its back-projected pixels to the surface - leave-one-out, because a model that already
+holds the frame at its old pose would keep it there.  A frame whose alignment fails keeps its pose and is counted.  It reads no flow, so
+it measures the poses against the geometry they produce - which the flow-based stages cannot; it needs disparities good enough to fuse:
+run it with --disp single_frame or multi_frame and --force once the networks exist.  --report adds `model_resid_before` and
+`model_resid_after` (the weighted rms distance of a frame to the model in voxels, averaged over the aligned frames: the opening pass of
+round 1 and the closing pass of the last round), `model_used` (the share of the valid pixels used), `model_failed`, and against stored
+poses `model_gt_rot`, `model_gt_trans` next to the pairwise and joint ones.  Its limits: the capture range is about the truncation band
+(--trunc voxels: the start must already be that close); its accuracy is bounded by the volume, a fraction of a voxel, so poses that
+are already better than that - exact disparities with good flows - are made worse, not better (profiles/tsdf_align_rate.md has the
+figures); on a planar scene the residual falls while the pose slides along the
+directions the surface does not constrain; the intrinsics are not refined, and there is no loop closure across tracks.  Without --model
+nothing changes, the bytes written included.
 """
 import argparse
 import os
@@ -220,14 +239,105 @@ def joint_line(acc):
     return res
 
 
+def model_loop(R, t, integrate, align, rounds=2):
+    """the leave-one-out loop of the model stage, Gauss-Seidel: for each round and each frame f = 1 .. tl - 1, vol = integrate(others, R, t)
+    - the frames `others` (all but f) at their current poses - and align(f, vol, R[f], t[f]) -> (R_f, t_f, stats (8) of
+    ops.tsdf_align_poses), taken where its status is 1.  Aligning a frame to a model that already holds it at its old pose would keep
+    it there; frame 0 stays the world.  R (tl, 3, 3), t (tl, 3) float32 -> R, t (copies), first, last: the stats (tl, 8) of every frame's
+    alignment in the first and in the last round (row 0: zeros)"""
+    R, t = np.array(R, dtype=np.float32), np.array(t, dtype=np.float32)
+    tl = len(R)
+    first, last = np.zeros((tl, 8), np.float32), np.zeros((tl, 8), np.float32)
+    for r in range(int(rounds)):
+        for f in range(1, tl):
+            vol = integrate([k for k in range(tl) if k != f], R, t)
+            Rf, tf, st = align(f, vol, R[f], t[f])
+            if r == 0:
+                first[f] = st
+            last[f] = st
+            if st[3] == 1:
+                R[f], t[f] = Rf, tf
+    return R, t, first, last
+
+
+def model_refine_track(disp, R, t, value, settings, rounds=2, iters=6, res=256, voxel=None, trunc_voxels=3.0, min_weight=1, tol=0.01,
+                       min_views=2, scale=None, damping=0.0, min_corr=64, device='cuda'):
+    """one track, float32 numpy in: frame-to-model refinement of its poses (ops.tsdf_align_poses) against its own volume.  The lattice
+    is placed once, from the incoming poses, as data/mesh.py places it (mesh.place_track); then model_loop, with the other frames
+    integrated into that lattice by mesh.integrate_placed and `iters` steps per alignment.  -> dict R (tl, 3, 3), t (tl, 3) float32
+    numpy, first, last (tl, 8: see model_loop), voxel, trunc, grid - or None where the volume cannot be placed"""
+    from .. import ops
+    from . import mesh
+    disp = np.ascontiguousarray(disp, dtype=np.float32)
+    disp = disp.reshape(disp.shape[0], disp.shape[-2], disp.shape[-1])
+    place = mesh.place_track(disp, R, t, value, settings, res, voxel, trunc_voxels, tol, min_views, device)
+    if place is None:
+        return None
+    origin, vx, trunc, grid = place
+    dev = torch.device(device)
+    K = np.asarray(settings.K, dtype=np.float32)
+    d_disp = torch.from_numpy(disp).to(dev)
+    ws = torch.empty(ops.lib.fn('dis_tsdf_align_workspace')(1, disp.shape[1], disp.shape[2]), dtype=torch.uint8, device=dev)
+
+    def integrate(others, Rc, tc):
+        return mesh.integrate_placed(disp[others], Rc[others], tc[others], None if value is None else np.asarray(value)[others], settings,
+                                     place, device)
+
+    def align(f, vol, Rf, tf):
+        r = ops.tsdf_align_poses(vol['tsdf'], vol['weight'], origin, vx, trunc, d_disp[f:f + 1], K, settings.baseline,
+                                 torch.from_numpy(Rf[None].copy()).to(dev), torch.from_numpy(tf[None].copy()).to(dev), iters=iters, scale=scale,
+                                 damping=damping, min_corr=min_corr, min_weight=min_weight, workspace=ws)
+        return r['R'][0].cpu().numpy(), r['t'][0].cpu().numpy(), r['stats'][0].cpu().numpy()
+
+    Rn, tn, first, last = model_loop(R, t, integrate, align, rounds)
+    return dict(R=Rn, t=tn, first=first, last=last, voxel=vx, trunc=trunc, grid=grid)
+
+
+def model_terms(res, depth, stored=None):
+    """the sums one track adds to the report for the model stage.  res: the dict of model_refine_track -> dict: model_frames (the frames
+    aligned in the first and in the last round, over which the next three are summed), model_resid_before, model_resid_after (the
+    weighted rms distance to the model in voxels: the opening pass of round 1, the closing pass of the last round), model_used (the
+    share of the valid pixels that the closing pass uses), model_failed (frames whose last alignment failed); with stored poses
+    model_gt_pairs (all ordered pairs), model_gt_rot, model_gt_trans"""
+    first, last = res['first'][1:], res['last'][1:]
+    ok = (first[:, 3] == 1) & (last[:, 3] == 1)
+    r = {'model_frames': int(ok.sum()), 'model_failed': int((last[:, 3] != 1).sum()),
+         'model_resid_before': float((first[ok, 6] / res['voxel']).sum()), 'model_resid_after': float((last[ok, 2] / res['voxel']).sum()),
+         'model_used': float((last[ok, 0] / np.maximum(last[ok, 7], 1)).sum())}
+    if stored is not None:
+        tl = len(res['R'])
+        off = ~np.eye(tl, dtype=bool)
+        (Rm, tm), (Rs, ts) = relative_poses(res['R'], res['t']), relative_poses(*stored)
+        r['model_gt_pairs'] = int(off.sum())
+        r['model_gt_rot'] = float(rotation_angle(Rm[off] @ np.swapaxes(Rs[off], -1, -2)).sum())
+        r['model_gt_trans'] = float((np.linalg.norm(tm[off] - ts[off], axis=-1) / depth).sum())
+    return r
+
+
+def model_line(acc):
+    """the sums of model_terms added over the tracks -> what the model stage adds to the dict that is printed"""
+    div = lambda a, b: a / b if b else float('nan')
+    n = acc.get('model_frames', 0)
+    res = {'model_resid_before': div(acc.get('model_resid_before', 0.0), n), 'model_resid_after': div(acc.get('model_resid_after', 0.0), n),
+           'model_used': div(acc.get('model_used', 0.0), n), 'model_failed': acc.get('model_failed', 0)}
+    if acc.get('model_gt_pairs'):
+        res['model_gt_rot'] = acc['model_gt_rot'] / acc['model_gt_pairs']
+        res['model_gt_trans'] = acc['model_gt_trans'] / acc['model_gt_pairs']
+    return res
+
+
 def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_corr=64, force=False, report=False, pack=False,
-                 device='cuda', joint=False, joint_iters=6):
+                 device='cuda', joint=False, joint_iters=6, model=False, model_rounds=2, model_iters=6, res=256, voxel=None, trunc_voxels=3.0,
+                 min_weight=1, tol=0.01, min_views=2):
     """Adds R (tl, 3, 3) and t (tl, 3) to the frames.npz of every track directory of data_root that has none (force: of all of them),
     each through a temporary file; the other arrays stay byte-identical.  pack: re-runs packed.pack_dataset.  Returns the number of
     tracks written, or with report=True - which also estimates the tracks it does not write - the dict of report_line with `tracks`,
     `written` and `failed_tracks` added (printed as one line).  The tracks that failed are printed by name.  joint: the pairwise result
     is refined by ops.refine_track_poses (joint_iters steps) before it is written - see the module's docstring; the report then also
-    carries the keys of joint_line and `joint_failed`, the tracks written with their pairwise poses."""
+    carries the keys of joint_line and `joint_failed`, the tracks written with their pairwise poses.  model: the poses - pairwise, or
+    joint - are then refined against the track's own volume by model_refine_track (model_rounds leave-one-out rounds of model_iters steps;
+    res, voxel, trunc_voxels, min_weight, tol, min_views as in data/mesh.py) before they are written; a track whose volume cannot be
+    placed keeps the poses it came with; the report then also carries the keys of model_line."""
     data_root = str(data_root)
     settings = load_settings(data_root)
     K = np.asarray(settings.K, dtype=np.float64)
@@ -266,16 +376,26 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
                     terms.update(joint_terms(Rj[b], tj[b], jst[b], depth, stored))
                 for key, v in terms.items():
                     acc[key] = acc.get(key, 0) + v
-            if not write:
+            if not (write or (model and report)):
                 continue
             if joint:
                 poses = starts[b]
                 if poses is not None and jst[b, 3] != 0:
                     poses = (Rj[b], tj[b])
-                elif poses is not None:
+                elif poses is not None and write:
                     joint_failed.append(d)
             else:
                 poses = compose_track(Rp[b], tp[b], ok[b])
+            if model and poses is not None:
+                mres = model_refine_track(disps[b], poses[0], poses[1], None, settings, model_rounds, model_iters, res, voxel, trunc_voxels,
+                                          min_weight, tol, min_views, device=device)
+                if mres is not None:
+                    poses = (mres['R'], mres['t'])
+                    if report:
+                        for key, v in model_terms(mres, depth, stored).items():
+                            acc[key] = acc.get(key, 0) + v
+            if not write:
+                continue
             if poses is None:
                 failed.append(d)
                 continue
@@ -291,15 +411,17 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
         packed.pack_dataset(data_root)
     if not report:
         return done
-    res = report_line(acc) if acc else {}
+    out = report_line(acc) if acc else {}
     if acc.get('joint_tracks'):
-        res.update(joint_line(acc))
-    res.update(tracks=len(todo), written=done, failed_tracks=len(failed))
+        out.update(joint_line(acc))
+    out.update(tracks=len(todo), written=done, failed_tracks=len(failed))
     if joint:
-        res.update(joint_failed=len(joint_failed))
+        out.update(joint_failed=len(joint_failed))
+    if model:
+        out.update(model_line(acc))
     print(f'poses from the {source} disparities over {data_root} (iters {iters}, scale {scale:g}, damping {damping:g}'
-          + (f', joint iters {joint_iters}' if joint else '') + '): ' + report_text(res, '.6g'))
-    return res
+          + (f', joint iters {joint_iters}' if joint else '') + (f', model rounds {model_rounds} iters {model_iters}' if model else '') + '): ' + report_text(out, '.6g'))
+    return out
 
 
 def main(argv=None):
@@ -316,9 +438,26 @@ def main(argv=None):
     ap.add_argument('--pack', action='store_true', help='also (re)write the packed files (data/packed.py)')
     ap.add_argument('--joint', action='store_true', help='refine the poses of a track jointly over all its ok pairs before they are written')
     ap.add_argument('--joint-iters', type=int, default=6, help='Gauss-Newton steps of the joint refinement (1 .. 64)')
+    ap.add_argument('--model', action='store_true', help="refine the poses against the track's own TSDF volume before they are written")
+    ap.add_argument('--model-rounds', type=int, default=2, help='leave-one-out rounds over the frames of a track')
+    ap.add_argument('--model-iters', type=int, default=6, help='Gauss-Newton steps of one alignment (1 .. 64)')
+    size = ap.add_mutually_exclusive_group()
+    size.add_argument('--res', type=int, default=256, help='--model: lattice points along the longest side of the padded box')
+    size.add_argument('--voxel', type=float, default=None, help='--model: the lattice spacing, instead of --res')
+    ap.add_argument('--trunc', type=float, default=3.0, help='--model: the truncation distance in voxels')
+    ap.add_argument('--min-weight', type=int, default=1, help='--model: frames that must observe each of the eight lattice points of a cell')
+    ap.add_argument('--tol', type=float, default=0.01, help='--model: relative depth tolerance of the cross-view check that places the volume')
+    ap.add_argument('--min-views', type=int, default=2, help='--model: agreeing frames a point needs to count for the placement')
     a = ap.parse_args(argv)
+    if a.voxel is not None and not a.voxel > 0:
+        ap.error('--voxel must be positive')
+    if not a.trunc > 0:
+        ap.error('--trunc must be positive')
+    if a.model_rounds < 1:
+        ap.error('--model-rounds must be at least 1')
     r = presave_pose(a.root, a.disp, a.iters, a.scale, a.damping, a.min_corr, force=a.force, report=a.report, pack=a.pack, joint=a.joint,
-                     joint_iters=a.joint_iters)
+                     joint_iters=a.joint_iters, model=a.model, model_rounds=a.model_rounds, model_iters=a.model_iters, res=a.res, voxel=a.voxel,
+                     trunc_voxels=a.trunc, min_weight=a.min_weight, tol=a.tol, min_views=a.min_views)
     print(f'{r["written"] if a.report else r} tracks written under {a.root}')
 
 

@@ -178,6 +178,8 @@ SIGS = {
     'dis_tsdf_mesh': 'pppp' + 'f' + 'iii' + 'p' + 'iii' + 'pl' + 'p',
     'dis_tsdf_raycast_workspace': 'iii',
     'dis_tsdf_raycast': 'pppp' + 'f' + 'i' + 'ppp' + 'ff' + 'i' + 'ppp' + 'iiiiii' + 'pl' + 'p',
+    'dis_tsdf_align_workspace': 'iii',
+    'dis_tsdf_align_poses': 'ppp' + 'ff' + 'i' + 'pp' + 'f' + 'pp' + 'i' + 'ff' + 'i' + 'ppp' + 'iiiiii' + 'pl' + 'p',
     'dis_allreduce_unique_id': 'p',
     'dis_allreduce_init': 'ppii',
     'dis_allreduce_sum_f32': 'pplip',
@@ -188,7 +190,7 @@ _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_wor
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace', 'dis_geo_loss_bwd_det_workspace',
              'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace',
              'dis_pose_joint_workspace',
-             'dis_tsdf_mesh_workspace', 'dis_tsdf_raycast_workspace'}
+             'dis_tsdf_mesh_workspace', 'dis_tsdf_raycast_workspace', 'dis_tsdf_align_workspace'}
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}
 _lib = None

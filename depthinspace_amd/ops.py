@@ -2902,7 +2902,8 @@ def refine_track_poses(disp, flow, K, baseline, R_init, t_init, pair_use=None, i
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# volumetric fusion (csrc/tsdf.hip, csrc/raycast.hip; data/mesh.py writes the meshes, data/raycast.py the per-frame maps)
+# volumetric fusion (csrc/tsdf.hip, csrc/raycast.hip, csrc/tsdf_align.hip; data/mesh.py writes the meshes, data/raycast.py the per-frame
+# maps, data/presave_pose.py --model refines the poses against the volume)
 # ----------------------------------------------------------------------------------------------------------------------
 def tsdf_integrate(disp, R, t, K, baseline, value=None, *, origin, voxel, trunc, grid):
     """dis_tsdf_integrate: the disparity maps disp (tl, H, W) or (tl, 1, H, W) of ONE track, 1 <= tl <= 4, with the poses R (tl, 3, 3),
@@ -3034,4 +3035,59 @@ def tsdf_raycast(tsdf, weight, vvalue, origin, voxel, R, t, K, baseline, size, s
            'value': torch.empty((nv, h, w), dtype=torch.float32, device=dev)}
     lib.call('dis_tsdf_raycast', tsdf, weight, vvalue, lib.host_floats(origin), voxel, min_weight, R, t, lib.host_floats(K4), baseline, step,
              variant, res['disp'], res['normal'], res['value'], nv, h, w, nx, ny, nz, workspace, int(workspace.numel()))
+    return res
+
+
+def tsdf_align_poses(tsdf, weight, origin, voxel, trunc, disp, K, baseline, R_init, t_init, iters=6, scale=None, damping=0.0, min_corr=64,
+                     min_weight=1, workspace=None):
+    """dis_tsdf_align_poses: frame-to-model pose refinement.  The volume tsdf (nz, ny, nx) fp32, weight (nz, ny, nx) uint8 of
+    tsdf_integrate on the lattice origin, voxel with the truncation distance trunc, and nv views - disp (nv, H, W) or (nv, 1, H, W)
+    with the poses R_init (nv, 3, 3), t_init (nv, 3) (X_c = R X_w + t, 1 <= nv <= 64), intrinsics K (3 x 3, host) and the baseline -> the
+    pose of every view refined on the signed distance of its back-projected pixels to the volume's surface (include/dis_hip.h,
+    section "volumetric fusion"; tests/tsdf_align_ref.py restates it in numpy).  No flow is read.  A pixel is used where its disparity
+    is valid, its point lies in a cell whose eight lattice points have weight >= min_weight (1 .. 4) and the trilinear tsdf there is
+    inside (-1, 1).  `iters` (1 .. 64) Gauss-Newton steps, every pass weighted by 1 / (1 + e^2 / scale^2)^2 (scale: a length, default
+    trunc / 2); damping >= 0 adds damping * diag(H); a view with fewer than min_corr (>= 6) used pixels, or a singular system, fails and
+    keeps its last good state - R_init, t_init bit for bit if it fails in the first pass.  The start must lie within about the
+    truncation band of the answer.
+    -> a dict of device tensors: R (nv, 3, 3), t (nv, 3), stats (nv, 8) fp32 = {pixels used, mean weight, weighted rms residual (a
+    length), status (1 ok, 0 failed)} of the closing pass, {pixels used, mean weight, weighted rms residual} of the opening pass at
+    R_init, and the number of valid disparities.  A view's result does not depend on the other views of the call.  The inputs are
+    data: no autograd.  2 (iters + 1) launches on the current stream, no synchronisation; workspace: an optional uint8 tensor of at
+    least dis_tsdf_align_workspace(nv, H, W) bytes to reuse between calls (and what makes the call capturable without an allocation
+    besides the outputs)."""
+    _chk(tsdf, disp, R_init, t_init)
+    if not (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.is_contiguous()):
+        raise RuntimeError('tsdf_align_poses: weight must be a contiguous CUDA(HIP) tensor: the HIP path is the only path')
+    if tsdf.dim() != 3 or tuple(weight.shape) != tuple(tsdf.shape):
+        raise RuntimeError('tsdf_align_poses: tsdf and weight (nz, ny, nx) are expected')
+    if weight.dtype != torch.uint8:
+        raise RuntimeError('tsdf_align_poses: tsdf is float32, weight is uint8')
+    if not (disp.dim() == 3 or (disp.dim() == 4 and disp.shape[1] == 1)):
+        raise RuntimeError('tsdf_align_poses: disp (nv, H, W) or (nv, 1, H, W) is expected')
+    nv, h, w = int(disp.shape[0]), int(disp.shape[-2]), int(disp.shape[-1])
+    if tuple(R_init.shape) != (nv, 3, 3) or tuple(t_init.shape) != (nv, 3):
+        raise RuntimeError('tsdf_align_poses: R_init (nv, 3, 3) and t_init (nv, 3) are expected')
+    nz, ny, nx = (int(v) for v in tsdf.shape)
+    need = lib.fn('dis_tsdf_align_workspace')(nv, h, w)
+    if need < 0 or not all(2 <= g <= 1024 for g in (nx, ny, nz)):
+        raise lib.DisHipError(f'tsdf_align_poses: unsupported extents nv={nv} h={h} w={w} nx={nx} ny={ny} nz={nz}')
+    voxel, trunc, baseline, damping = float(voxel), float(trunc), float(baseline), float(damping)
+    iters, min_corr, min_weight = int(iters), int(min_corr), int(min_weight)
+    scale = trunc / 2 if scale is None else float(scale)
+    origin = [float(origin[0]), float(origin[1]), float(origin[2])]
+    K4 = _k4(K)
+    if not (all(_fin(v) for v in K4 + origin + [voxel, trunc, baseline, scale, damping]) and voxel > 0 and trunc > 0 and scale > 0
+            and damping >= 0 and K4[0] > 0 and K4[1] > 0 and baseline > 0 and 1 <= iters <= 64 and min_corr >= 6
+            and 1 <= min_weight <= 4):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'tsdf_align_poses: unsupported configuration voxel={voxel} trunc={trunc} origin={origin} K={K4} '
+                              f'baseline={baseline} iters={iters} scale={scale} damping={damping} min_corr={min_corr} '
+                              f'min_weight={min_weight}')
+    dev = disp.device
+    workspace = _workspace('tsdf_align_poses', need, workspace, dev)
+    res = {'R': torch.empty((nv, 3, 3), dtype=torch.float32, device=dev), 't': torch.empty((nv, 3), dtype=torch.float32, device=dev),
+           'stats': torch.empty((nv, 8), dtype=torch.float32, device=dev)}
+    lib.call('dis_tsdf_align_poses', tsdf, weight, lib.host_floats(origin), voxel, trunc, min_weight, disp, lib.host_floats(K4), baseline,
+             R_init, t_init, iters, scale, damping, min_corr, res['R'], res['t'], res['stats'], nv, h, w, nx, ny, nz, workspace,
+             int(workspace.numel()))
     return res

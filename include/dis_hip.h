@@ -1148,6 +1148,45 @@ int dis_tsdf_raycast(const float* tsdf, const unsigned char* weight, const float
                      float* disp, float* normal, float* value, int nv, int h, int w, int nx, int ny, int nz, void* workspace,
                      long workspace_bytes, void* stream);
 
+/* dis_tsdf_align_poses: frame-to-model pose refinement (csrc/tsdf_align.hip): the poses of nv views - a track's frames, say - refined
+ * against a volume, by Gauss-Newton on the signed distance of every view's back-projected pixels to the volume's surface.  No flow and
+ * no second frame are read.  tests/tsdf_align_ref.py restates it in numpy, operand order included.  Every per-pixel term is a fixed
+ * fp32 expression, converted to fp64 and added in fp64; the state and the solve are fp64, as in "track poses", and the layout of the 30
+ * sums, the reduction and the 6 x 6 step are those of dis_track_poses.  fb = fx baseline, s2 = scale scale and tv = trunc / voxel are
+ * formed in fp32 on the host.  Per view, per pass at the state (R, t) rounded to fp32, the pixel (u, v) with disparity d:
+ *   skipped unless d is valid.  P = (z ((float(u) - cx) / fx), z ((float(v) - cy) / fy), z), z = fb / d.
+ *   q = P - t; X_k = (R[0][k] q0 + R[1][k] q1) + R[2][k] q2 (the world point); g_a = (X_a - origin_a) / voxel.
+ *   The cell and its inside test are those of dis_tsdf_raycast: skipped unless 0 <= g_a < float(n_a - 1) on the three axes; i_a =
+ *   floor(g_a), f_a = g_a - float(i_a); skipped unless the eight corner weights are >= min_weight.
+ *   s = the trilinear tsdf (x, then y, then z, each a + f (b - a)); skipped unless |s| < 1: saturated free space has no gradient.
+ *   (g0, g1, g2) = the gradient of the interpolant in lattice units, the expressions of dis_tsdf_raycast's normal before its division.
+ *   e = trunc s, the residual: a length.  m_a = tv g_a; n_r = (R[r][0] m0 + R[r][1] m1) + R[r][2] m2, the gradient of e in the camera's
+ *   frame.  J = (n1 P2 - n2 P1, n2 P0 - n0 P2, n0 P1 - n1 P0, -n0, -n1, -n2): rotation 0 .. 2, translation 3 .. 5 of the left
+ *   perturbation R <- dR R, t <- dR t + delta.  wgt = g g with g = 1 / (1 + (e e) / s2), in every pass: the start is assumed near.
+ *   H_pq += (wgt J_p) J_q for p <= q, g_p += (wgt J_p) e, S_w += wgt, S_c += wgt (e e), n += 1.
+ * The step: as in dis_track_poses - fewer than min_corr used pixels, or a pivot of the Cholesky factorisation of H + damping diag(H)
+ * that is not > 0 and finite, fails the view, which keeps its last good state: R_init, t_init bit for bit if the first pass fails.
+ * tsdf, weight (nz, ny, nx) as dis_tsdf_integrate writes them, disp (nv, h, w), R_init (nv, 3, 3), t_init (nv, 3) (X_c = R X_w + t):
+ * DEVICE.  origin3_host, K4_host: HOST.  Outputs, DEVICE, every element written: R (nv, 3, 3), t (nv, 3), stats (nv, 8) fp32 =
+ * {n, S_w / n, sqrt(S_c / S_w), status (1 ok, 0 failed)} of the closing pass, {n, S_w / n, sqrt(S_c / S_w)} of the opening pass at
+ * R_init, the number of valid disparities of the view (a ratio without a denominator is 0).
+ * iters + 1 launches of tsdf_align_accum_kernel (bpp workgroups of 256 lanes per view, a wave per 8 x 8 patch of a 16 x 16 tile, the
+ * tiles of a view taken in turn by its workgroups; one record of 32 doubles per workgroup) and iters + 1 of tsdf_align_solve_kernel (a
+ * wave per view; the records added in ascending order), in turn on the given stream; the last pair only measures.  The hand-off is
+ * the launch boundary alone: no atomics, no flags polled between workgroups, no allocation, no synchronisation - two calls give the
+ * same bits, a view's result does not depend on the other views of the call, and the call is capturable.  The first accumulate launch
+ * reads R_init directly: the workspace needs no initialisation.
+ * workspace: dis_tsdf_align_workspace(nv, h, w) BYTES (-1: unsupported extents), 16-byte aligned.
+ * Checks, in this order, all before any launch: a NULL pointer -> DIS_ERR_NULL; nv outside 1 .. 64, h or w outside 2 .. 8192, nx, ny or
+ * nz outside 2 .. 1024 -> DIS_ERR_BAD_SHAPE; iters outside 1 .. 64, scale, scale scale, voxel, trunc, trunc / voxel, fx, fy, baseline or
+ * fx baseline not positive and finite, damping negative or not finite, min_corr < 6, min_weight outside 1 .. 4, cx, cy or a component of
+ * the origin not finite, workspace_bytes below dis_tsdf_align_workspace(...), a misaligned workspace -> DIS_ERR_UNSUPPORTED. */
+long dis_tsdf_align_workspace(int nv, int h, int w);
+int dis_tsdf_align_poses(const float* tsdf, const unsigned char* weight, const float* origin3_host, float voxel, float trunc,
+                         int min_weight, const float* disp, const float* K4_host, float baseline, const float* R_init,
+                         const float* t_init, int iters, float scale, float damping, int min_corr, float* R, float* t, float* stats,
+                         int nv, int h, int w, int nx, int ny, int nz, void* workspace, long workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- optimiser ----------------- */
 
 /* torch.optim.Adam(lr, betas=(0.9,0.999), eps=1e-8) on a flat fp32 buffer (reference train_val.py:55-56).
