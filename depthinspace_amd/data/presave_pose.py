@@ -12,6 +12,7 @@ whose pairs failed is listed as failed and left as it is.
 
     python -m depthinspace_amd.data.presave_pose ROOT [--disp gt|sgm|single_frame|multi_frame] [--iters N] [--scale S] [--damping D]
                                                       [--min-corr N] [--force] [--report] [--pack] [--joint] [--joint-iters N]
+                                                      [--pairwise flow|disp]
                                                       [--model] [--model-rounds N] [--model-iters N] [--res N | --voxel V]
                                                       [--trunc VOXELS] [--min-weight N] [--tol T] [--min-views N]
 
@@ -21,6 +22,16 @@ pixels a pair uses, its mean weight and weighted rms residual in pixels, and the
 |t_ji + R_ji t_ij| over the median depth of the track, averaged over the unordered pairs: a quality figure that needs no ground truth.
 Where a track stored poses before the run, the rotation angle and the translation error (over the median depth) of the estimated
 relative poses against the stored ones are added.
+
+--pairwise disp takes the pairwise stage from the disparity maps alone, ops.disp_align_poses (dis_disp_align_poses; include/dis_hip.h,
+section "disparity alignment"): direct coarse-to-fine alignment of frame i's disparity map onto frame j's, from the identity, with no
+flow - no flow.npz is needed, and data/presave_flow.py --source geometry can then write one from the poses.  It is what to use where
+the images carry no texture for an image-based flow (flat-shaded surfaces: there the flow-based poses are wrong by the size of the
+motion itself), and what gives --model a start inside its truncation band.  It runs at its own defaults (levels, schedule, a robust
+scale of 0.3 px of disparity); --iters and --scale belong to the flow-based stage, --damping and --min-corr to both.  Its limits: the scene must be static;
+the disparity noise must be small against the disparity (at 10 % it breaks down); a planar fronto-parallel scene leaves three of the six
+directions open and the pair fails at a zero pivot; holes take no part.  The outputs, the composition, --report, --force, --pack and
+--model are those of the flow-based stage; --joint still reads flow.npz and says so where there is none.
 
 Without --joint this is pairwise and nothing more: the pairs are independent, and only the pairs with frame 0 set the stored poses.
 --joint adds a second stage, ops.refine_track_poses (dis_refine_track_poses): one pose per frame, frame 0 fixed, --joint-iters
@@ -200,6 +211,15 @@ def estimate_pairs(disps, flows, settings, iters=6, scale=1.0, damping=0.0, min_
     return tuple(r[k].cpu().numpy() for k in ('R_pair', 't_pair', 'stats'))
 
 
+def align_pairs(disps, settings, damping=0.0, min_corr=64, device='cuda'):
+    """estimate_pairs without flows: a list of (tl, H, W) disparities of tracks of one length -> R_pair, t_pair, stats float32 numpy (one
+    call of ops.disp_align_poses at its default levels and schedule)"""
+    from .. import ops
+    d = torch.from_numpy(np.ascontiguousarray(np.stack(disps), dtype=np.float32)).to(torch.device(device))
+    r = ops.disp_align_poses(d, np.asarray(settings.K, dtype=np.float32), settings.baseline, damping=damping, min_corr=min_corr)
+    return tuple(r[k].cpu().numpy() for k in ('R_pair', 't_pair', 'stats'))
+
+
 def refine_tracks(disps, flows, settings, R_init, t_init, use, iters=6, scale=1.0, damping=0.0, min_corr=64, device='cuda'):
     """the lists of estimate_pairs with R_init (n, tl, 3, 3), t_init (n, tl, 3) float32 and use (n, tl, tl) bool -> R (n, tl, 3, 3), t (n, tl, 3),
     pair_stats (n, tl, tl, 4), track_stats (n, 4) float32 numpy (one call of ops.refine_track_poses)"""
@@ -328,7 +348,7 @@ def model_line(acc):
 
 def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_corr=64, force=False, report=False, pack=False,
                  device='cuda', joint=False, joint_iters=6, model=False, model_rounds=2, model_iters=6, res=256, voxel=None, trunc_voxels=3.0,
-                 min_weight=1, tol=0.01, min_views=2):
+                 min_weight=1, tol=0.01, min_views=2, pairwise='flow'):
     """Adds R (tl, 3, 3) and t (tl, 3) to the frames.npz of every track directory of data_root that has none (force: of all of them),
     each through a temporary file; the other arrays stay byte-identical.  pack: re-runs packed.pack_dataset.  Returns the number of
     tracks written, or with report=True - which also estimates the tracks it does not write - the dict of report_line with `tracks`,
@@ -337,7 +357,10 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
     carries the keys of joint_line and `joint_failed`, the tracks written with their pairwise poses.  model: the poses - pairwise, or
     joint - are then refined against the track's own volume by model_refine_track (model_rounds leave-one-out rounds of model_iters steps;
     res, voxel, trunc_voxels, min_weight, tol, min_views as in data/mesh.py) before they are written; a track whose volume cannot be
-    placed keeps the poses it came with; the report then also carries the keys of model_line."""
+    placed keeps the poses it came with; the report then also carries the keys of model_line.  pairwise 'disp': the pairwise stage is
+    align_pairs and reads no flow.npz; joint still does."""
+    if pairwise not in ('flow', 'disp'):
+        raise ValueError(f'pairwise must be flow or disp, not {pairwise!r}')
     data_root = str(data_root)
     settings = load_settings(data_root)
     K = np.asarray(settings.K, dtype=np.float64)
@@ -356,9 +379,16 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
             if disps and disp.shape != disps[0].shape:
                 break
             disps.append(disp)
-            flows.append(load_flow(todo[k][0], disp.shape[0]))
+            if pairwise == 'flow' or joint:
+                if joint and not os.path.exists(os.path.join(todo[k][0], 'flow.npz')):
+                    raise ValueError(f'{todo[k][0]}: --joint reads flow.npz and there is none (data/presave_flow.py writes it; with '
+                                     f'--pairwise disp run without --joint first, then presave_flow --source geometry)')
+                flows.append(load_flow(todo[k][0], disp.shape[0]))
             k += 1
-        Rp, tp, st = estimate_pairs(disps, flows, settings, iters, scale, damping, min_corr, device)
+        if pairwise == 'disp':
+            Rp, tp, st = align_pairs(disps, settings, damping, min_corr, device)
+        else:
+            Rp, tp, st = estimate_pairs(disps, flows, settings, iters, scale, damping, min_corr, device)
         ok = st[..., 3] != 0
         if joint:
             # the start: the pairwise result chained from frame 0; a track that no chain covers takes no part (no pair is used: it fails)
@@ -419,7 +449,8 @@ def presave_pose(data_root, source='sgm', iters=6, scale=1.0, damping=0.0, min_c
         out.update(joint_failed=len(joint_failed))
     if model:
         out.update(model_line(acc))
-    print(f'poses from the {source} disparities over {data_root} (iters {iters}, scale {scale:g}, damping {damping:g}'
+    stage = 'aligned disparity maps' if pairwise == 'disp' else f'iters {iters}, scale {scale:g}'
+    print(f'poses from the {source} disparities over {data_root} ({stage}, damping {damping:g}'
           + (f', joint iters {joint_iters}' if joint else '') + (f', model rounds {model_rounds} iters {model_iters}' if model else '') + '): ' + report_text(out, '.6g'))
     return out
 
@@ -448,6 +479,8 @@ def main(argv=None):
     ap.add_argument('--min-weight', type=int, default=1, help='--model: frames that must observe each of the eight lattice points of a cell')
     ap.add_argument('--tol', type=float, default=0.01, help='--model: relative depth tolerance of the cross-view check that places the volume')
     ap.add_argument('--min-views', type=int, default=2, help='--model: agreeing frames a point needs to count for the placement')
+    ap.add_argument('--pairwise', default='flow', choices=['flow', 'disp'],
+                    help='the pairwise stage: disparities and flow.npz (flow), or the disparity maps alone (disp: no flow.npz is needed)')
     a = ap.parse_args(argv)
     if a.voxel is not None and not a.voxel > 0:
         ap.error('--voxel must be positive')
@@ -457,7 +490,7 @@ def main(argv=None):
         ap.error('--model-rounds must be at least 1')
     r = presave_pose(a.root, a.disp, a.iters, a.scale, a.damping, a.min_corr, force=a.force, report=a.report, pack=a.pack, joint=a.joint,
                      joint_iters=a.joint_iters, model=a.model, model_rounds=a.model_rounds, model_iters=a.model_iters, res=a.res, voxel=a.voxel,
-                     trunc_voxels=a.trunc, min_weight=a.min_weight, tol=a.tol, min_views=a.min_views)
+                     trunc_voxels=a.trunc, min_weight=a.min_weight, tol=a.tol, min_views=a.min_views, pairwise=a.pairwise)
     print(f'{r["written"] if a.report else r} tracks written under {a.root}')
 
 

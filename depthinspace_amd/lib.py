@@ -173,6 +173,9 @@ SIGS = {
     'dis_track_poses': 'ppp' + 'f' + 'i' + 'ff' + 'i' + 'ppp' + 'iiii' + 'pl' + 'p',
     'dis_pose_joint_workspace': 'iiii',
     'dis_refine_track_poses': 'ppp' + 'f' + 'ppp' + 'i' + 'ff' + 'i' + 'pppp' + 'iiii' + 'pl' + 'p',
+    'dis_disp_align_workspace': 'iiiii',
+    'dis_disp_align_poses': 'pp' + 'f' + 'i' + 'p' + 'ff' + 'i' + 'f' + 'ppp' + 'p' + 'iiii' + 'pl' + 'p',
+    'dis_rigid_flow': 'ppp' + 'p' + 'ff' + 'pp' + 'iiii' + 'p',
     'dis_tsdf_integrate': 'pppp' + 'f' + 'pp' + 'ff' + 'ppp' + 'iiiiii' + 'p',
     'dis_tsdf_mesh_workspace': 'iii',
     'dis_tsdf_mesh': 'pppp' + 'f' + 'iii' + 'p' + 'iii' + 'pl' + 'p',
@@ -189,7 +192,7 @@ _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_wor
              'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace', 'dis_geo_loss_bwd_det_workspace',
              'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace',
-             'dis_pose_joint_workspace',
+             'dis_pose_joint_workspace', 'dis_disp_align_workspace',
              'dis_tsdf_mesh_workspace', 'dis_tsdf_raycast_workspace', 'dis_tsdf_align_workspace'}
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float, 'd': ctypes.c_double}
@@ -214,6 +217,10 @@ class RenderOut(ctypes.Structure):   # include/dis_hip.h: DisRenderOut (device p
 
 class FlowDebug(ctypes.Structure):   # include/dis_hip.h: DisFlowDebug (device pointers, NULL: not wanted; the level of `warp`; the variant)
     _fields_ = [(n_, ctypes.c_void_p) for n_ in ('pyr', 'warp', 'levels')] + [('level', ctypes.c_int), ('variant', ctypes.c_int)]
+
+
+class DispAlignDebug(ctypes.Structure):   # include/dis_hip.h: DisDispAlignDebug (device pointers, NULL: not wanted; the level of `maps`)
+    _fields_ = [(n_, ctypes.c_void_p) for n_ in ('pyr', 'maps', 'sums')] + [('level', ctypes.c_int)]
 
 
 class FuseOut(ctypes.Structure):   # include/dis_hip.h: DisFuseOut (device pointers; point and dnormal may be NULL)
@@ -340,3 +347,8 @@ def call(name, *args, _soft=False):
 def host_floats(vals):
     vals = [float(v) for v in vals]
     return (ctypes.c_float * len(vals))(*vals)
+
+
+def host_ints(vals):
+    vals = [int(v) for v in vals]
+    return (ctypes.c_int * len(vals))(*vals)

@@ -2902,6 +2902,112 @@ def refine_track_poses(disp, flow, K, baseline, R_init, t_init, pair_use=None, i
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# disparity alignment (csrc/disp_align.hip; data/presave_pose.py --pairwise disp, data/presave_flow.py --source geometry)
+# ----------------------------------------------------------------------------------------------------------------------
+DISP_ALIGN_ITERS = (10, 6, 4, 4, 4, 4)   # steps per level, finest first
+
+
+def disp_align_levels(h, w):
+    """the default number of pyramid levels of disp_align_poses: a further halving while the next level keeps min(h, w) >= 24"""
+    levels = 1
+    while levels < 6 and min(int(h) >> levels, int(w) >> levels) >= 24:
+        levels += 1
+    return levels
+
+
+def disp_align_level_sizes(h, w, levels):
+    """[(h_0, w_0), (h_1, w_1), ...] of dis_disp_align_poses' pyramid: every level halves the one before, rounding down"""
+    return [(int(h) >> l, int(w) >> l) for l in range(int(levels))]
+
+
+def disp_align_poses(disp, K, baseline, levels=None, iters=None, scale=0.3, damping=0.0, min_corr=64, jump=0.15, workspace=None,
+                     want_debug=False, debug_level=0):
+    """dis_disp_align_poses: the disparity maps disp (n, tl, H, W) or (n, tl, 1, H, W) of n tracks with the intrinsics K (3 x 3, host:
+    numpy or a CPU tensor) and the baseline -> the relative pose of every ordered pair of frames, from the disparity maps alone - no flow
+    is read (include/dis_hip.h, section "disparity alignment"; tests/disp_align_ref.py restates it in numpy):
+    X_j = R_pair[b, i, j] X_i + t_pair[b, i, j].  Direct coarse-to-fine alignment of frame i's disparity map onto frame j's: Gauss-Newton
+    from the identity on the residual in disparity, over a pyramid of `levels` (1 .. 6; default: halved while min(h, w) >= 24 is kept)
+    with iters[l] (0 .. 64, not all 0; finest first; default (10, 6, 4, 4, 4, 4)) steps at level l, the coarsest level first; after the
+    first step the residuals are weighted by 1 / (1 + e^2 / scale^2)^2 (scale > 0, in pixels of disparity); a pixel is not used next to
+    a relative disparity step of `jump` (in (0, 1)) or more, or where its residual exceeds 2 jump of the predicted disparity; damping >= 0
+    adds damping * diag(H); a pair with fewer than min_corr (>= 6) usable pixels, or a singular system - a fronto-parallel plane -,
+    fails and keeps its last good state.  The scene is taken to be static.
+    -> a dict of device tensors: R_pair (n, tl, tl, 3, 3), t_pair (n, tl, tl, 3), stats (n, tl, tl, 4) fp32 = {pixels used, mean weight,
+    weighted rms residual in pixels of disparity, status (1 ok, 0 failed)} as track_poses gives them; the diagonal holds the identity.
+    want_debug: also a dict with pyr (list over the levels from 1, of (n, tl, h_l, w_l)), maps ((n, tl, h_l, w_l, 4) = D, Dx, Dy, good of
+    level debug_level) and sums ((passes, n, tl, tl, 30) fp64: the 30 sums of every pass).  The inputs are data: no autograd.
+    2 levels - 1 + 2 (sum(iters) + 1) launches on the current stream, no synchronisation; workspace: an optional uint8 tensor of at least
+    dis_disp_align_workspace(...) bytes to reuse between calls (and what makes the call capturable without an allocation besides the
+    outputs)."""
+    _chk(disp)
+    n, tl, h, w = _track_dims('disp_align_poses', disp)
+    levels = disp_align_levels(h, w) if levels is None else int(levels)
+    need = lib.fn('dis_disp_align_workspace')(n, tl, h, w, levels)
+    if need < 0:
+        raise lib.DisHipError(f'dis_disp_align_workspace: unsupported extents n={n} tl={tl} h={h} w={w} levels={levels}')
+    iters = [int(v) for v in (DISP_ALIGN_ITERS[:levels] if iters is None else iters)]
+    scale, damping, min_corr, jump, baseline = float(scale), float(damping), int(min_corr), float(jump), float(baseline)
+    K4 = _k4(K)
+    if not (len(iters) == levels and all(0 <= v <= 64 for v in iters) and sum(iters) > 0 and _fin(scale) and scale > 0 and _fin(damping)
+            and damping >= 0 and min_corr >= 6 and 0.0 < jump < 1.0 and all(_fin(v) for v in K4) and K4[0] > 0 and K4[1] > 0
+            and _fin(baseline) and baseline > 0 and 0 <= int(debug_level) < levels):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'disp_align_poses: unsupported configuration levels={levels} iters={iters} scale={scale} damping={damping} '
+                              f'min_corr={min_corr} jump={jump} K={K4} baseline={baseline} debug_level={debug_level}')
+    dev = disp.device
+    workspace = _workspace('disp_align_poses', need, workspace, dev)
+    res = {'R_pair': torch.empty((n, tl, tl, 3, 3), dtype=torch.float32, device=dev),
+           't_pair': torch.empty((n, tl, tl, 3), dtype=torch.float32, device=dev),
+           'stats': torch.empty((n, tl, tl, 4), dtype=torch.float32, device=dev)}
+    D, bufs = None, None
+    sizes = disp_align_level_sizes(h, w, levels)
+    if want_debug:
+        D = lib.DispAlignDebug()
+        D.level = int(debug_level)
+        bufs = {'pyr': torch.empty(max(1, sum(n * tl * a * b for a, b in sizes[1:])), dtype=torch.float32, device=dev),
+                'maps': torch.empty((n, tl) + sizes[int(debug_level)] + (4,), dtype=torch.float32, device=dev),
+                'sums': torch.empty((sum(iters) + 1, n, tl, tl, 30), dtype=torch.float64, device=dev)}
+        for k_, t_ in bufs.items():
+            setattr(D, k_, t_.data_ptr())
+    lib.call('dis_disp_align_poses', disp, lib.host_floats(K4), baseline, levels, lib.host_ints(iters), scale, damping, min_corr, jump,
+             res['R_pair'], res['t_pair'], res['stats'], _ct.addressof(D) if D is not None else None, n, tl, h, w, workspace,
+             int(workspace.numel()))
+    if not want_debug:
+        return res
+    dbg = {'maps': bufs['maps'], 'sums': bufs['sums'], 'pyr': []}
+    o = 0
+    for a, b in sizes[1:]:
+        dbg['pyr'].append(bufs['pyr'][o:o + n * tl * a * b].view(n, tl, a, b))
+        o += n * tl * a * b
+    return res, dbg
+
+
+def rigid_flow(disp, R, t, K, baseline, tol=0.01, want_visible=False):
+    """dis_rigid_flow: the flow that the disparity maps disp (n, tl, H, W) or (n, tl, 1, H, W) and the frame poses R (n, tl, 3, 3),
+    t (n, tl, 3) (X_c = R X_w + t) of n static tracks imply, with the intrinsics K (3 x 3, host) and the baseline -> (n, tl * tl, 2, H, W)
+    fp32 in the `_flow_stacked` layout of dense_flow (entry i * tl + j the flow from frame i to frame j, channel 0 along x), zeros on the
+    diagonal (include/dis_hip.h, section "disparity alignment"; tests/disp_align_ref.py restates it in numpy).  A pixel without a valid
+    disparity (finite and > 0), or whose point lies behind camera j, gets zeros.  want_visible: also (n, tl * tl, H, W) uint8, 1 where the
+    pixel's point falls inside frame j and frame j's disparity at the nearest pixel agrees with the point's within the relative
+    tolerance tol in (0, 1) (fuse_track's).  The inputs are data: no autograd.  One launch on the current stream, no synchronisation,
+    no workspace: capturable once the outputs exist."""
+    _chk(disp, R, t)
+    n, tl, h, w = _track_dims('rigid_flow', disp)
+    if tuple(R.shape) != (n, tl, 3, 3) or tuple(t.shape) != (n, tl, 3):
+        raise RuntimeError('rigid_flow: R (n, tl, 3, 3) and t (n, tl, 3) are expected')
+    if lib.fn('dis_pose_workspace')(n, tl, h, w) < 0:   # the extents of track_poses
+        raise lib.DisHipError(f'rigid_flow: unsupported extents n={n} tl={tl} h={h} w={w}')
+    tol, baseline = float(tol), float(baseline)
+    K4 = _k4(K)
+    if not (0.0 < tol < 1.0 and all(_fin(v) for v in K4) and K4[0] > 0 and K4[1] > 0 and _fin(baseline) and baseline > 0):
+        raise lib.DisHipError(f'rigid_flow: unsupported configuration tol={tol} K={K4} baseline={baseline}')   # before any allocation
+    dev = disp.device
+    flow = torch.empty((n, tl * tl, 2, h, w), dtype=torch.float32, device=dev)
+    visible = torch.empty((n, tl * tl, h, w), dtype=torch.uint8, device=dev) if want_visible else None
+    lib.call('dis_rigid_flow', disp, R, t, lib.host_floats(K4), baseline, tol, flow, visible, n, tl, h, w)
+    return (flow, visible) if want_visible else flow
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # volumetric fusion (csrc/tsdf.hip, csrc/raycast.hip, csrc/tsdf_align.hip; data/mesh.py writes the meshes, data/raycast.py the per-frame
 # maps, data/presave_pose.py --model refines the poses against the volume)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -1033,6 +1033,81 @@ int dis_refine_track_poses(const float* disp, const float* flow, const float* K4
                            float* R, float* t, float* pair_stats, float* track_stats, int n, int tl, int h, int w, void* workspace,
                            long workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- disparity alignment ------- */
+
+/* The relative camera pose of every ordered pair of frames of a track from its disparity maps ALONE (csrc/disp_align.hip): direct
+ * coarse-to-fine alignment of frame i's disparity map onto frame j's, Gauss-Newton on the residual in disparity, from the identity.  No
+ * flow is read: on flat-shaded surfaces an image-based flow finds nothing, the disparity maps carry the geometry.  The residual is in
+ * disparity (pixels), not in metres, so that a disparity noise weighs every depth alike.  Conventions and outputs are those of
+ * dis_track_poses: X_j = R_ij X_i + t_ij.  tests/disp_align_ref.py restates it in numpy, operand order included.  fb = fx baseline,
+ * s2 = scale scale, jump2 = 2 jump are formed in fp32 on the host; every per-pixel operation below is one fp32 operation.
+ *   valid      a disparity that is finite and > 0.
+ *   pyramid    per frame.  Level 0 is the input; level l + 1 has floor(h_l / 2) x floor(w_l / 2) cells (an odd last row or column is
+ *              dropped).  With a[0 .. 4) the block's disparities in the order 00, 01, 10, 11 (row, column): m = the largest valid one
+ *              (0 with none); a cell is the sum of the valid a[k] >= 0.9f m, added in that order from 0, divided by their number - the
+ *              nearer surface wins, nothing is averaged across a depth edge -, 0 with none.  Disparities stay in full-resolution pixels
+ *              on every level: z = fb / d everywhere.  Intrinsics (host, fp32): fx_l = fx_{l-1} / 2, cx_l = (cx_{l-1} - 0.5) / 2, y alike.
+ *   maps       per frame and level, one float4 per pixel {D, Dx, Dy, good}: D the disparity, Dx = 0.5 (d(x + 1) - d(x - 1)),
+ *              Dy = 0.5 (d(y + 1) - d(y - 1)); good (1.0) iff the pixel has its four neighbours inside the image, all five are valid,
+ *              |Dx| < jump D and |Dy| < jump D; all four are 0 where not good.
+ *   state      (R, t) per pair in fp64, set to the identity by the call itself and carried across the levels unchanged.  A pass at
+ *              level l uses its fp32 rounding and the level's intrinsics.  For pixel (u, v) of frame i's level l with a valid d:
+ *              z = fb / d, P = (z ((u - cx_l) / fx_l), z ((v - cy_l) / fy_l), z); Y[c] = ((R[c][0] P0 + R[c][1] P1) + R[c][2] P2) + t[c];
+ *              skipped unless Y2 > 0.  iz = 1 / Y2, px = Y0 iz, py = Y1 iz, u' = fx_l px + cx_l, v' = fy_l py + cy_l.
+ *   target     us = u' + 2^-6, vs = v' + 2^-6; skipped unless 0 <= us < w_l - 1 and 0 <= vs < h_l - 1 (false for NaN); x0 = floor(us),
+ *              y0 = floor(vs); skipped unless the maps of frame j are good at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1).
+ *              ax = u' - x0, ay = v' - y0 (>= -2^-6: the cell's own interpolant, continued), bx = 1 - ax, by = 1 - ay; D, Gx, Gy are
+ *              (m00 bx + m01 ax) by + (m10 bx + m11 ax) ay of the three maps.  (The 2^-6: at the identity every target lies on an
+ *              integer up to rounding; with the cells' boundary there the last bit would choose the cell, and with it the four taps.)
+ *   residual   pred = fb iz, e = D - pred; skipped unless |e| < jump2 pred.
+ *   Jacobian   g0 = Gx (fx_l iz), g1 = Gy (fy_l iz), g2 = pred iz - (g0 Y0 + g1 Y1) iz;
+ *              J = (Y1 g2 - Y2 g1, Y2 g0 - Y0 g2, Y0 g1 - Y1 g0, g0, g1, g2) over (omega, nu) of a left perturbation.
+ *   weight     1 in the first pass of the coarsest level, else q q with q = 1 / (1 + (e e) / s2).
+ *   sums       the 30 of dis_track_poses with the one row J: H_pq = sum (weight J[p]) J[q], g_p = sum (weight J[p]) e, S_w = sum weight,
+ *              S_c = sum weight (e e), n; every term formed in fp32 and added in fp64.
+ *   schedule   iters_host[l] steps at level l (iters_host: HOST, `levels` ints, finest first), the coarsest level first; the step and
+ *              its failure are those of dis_track_poses (n < min_corr, or a pivot that is not > 0 and finite: the pair keeps its last
+ *              good state and takes no further step at any level).  One closing pass at level 0, weighted, gives the statistics.
+ * disp (n, tl, h, w): DEVICE.  K4_host = {fx, fy, cx, cy}: HOST.  Outputs, DEVICE, every element written: R_pair (n, tl, tl, 3, 3),
+ * t_pair (n, tl, tl, 3), stats (n, tl, tl, 4) = {n, S_w / n, sqrt(S_c / S_w), status} of the closing pass, as dis_track_poses writes them;
+ * the diagonal is the identity, zeros and {0, 0, 0, 1}.
+ * dbg: HOST struct, NULL in normal use; every pointer in it may be NULL.  pyr: the levels 1 .. levels - 1 one after another, level l
+ * as (n, tl, h_l, w_l); maps: (n, tl, h_l, w_l, 4) of level l = `level`; sums: (passes, n, tl, tl, 30) fp64, passes = sum iters + 1, zeros
+ * on the diagonal.
+ * Launches: one per level above 0 for the pyramid, one per level for the maps (a lane per cell, every frame in the grid); then one
+ * accumulate launch (a wave per 8 x 8 patch of frame i, 2 x 2 waves per workgroup, the workgroups of a pair taking its 16 x 16 tiles in
+ * turn; the reduction of dis_track_poses) and one solve launch per pass, every ordered pair of every track in each grid.  The hand-off
+ * is the launch boundary alone: no atomics, no flags, so two calls give the same bits.  No allocation, no synchronisation: capturable.
+ * workspace: dis_disp_align_workspace(n, tl, h, w, levels) BYTES (-1: unsupported extents or levels), 16-byte aligned, no initialisation.
+ * Checks, in this order, all before any launch: a NULL pointer other than dbg -> DIS_ERR_NULL; n < 1, tl outside 2 .. 4, h or w outside
+ * 2 .. 8192, n tl tl 2 h w >= 2^31 -> DIS_ERR_BAD_SHAPE; levels outside 1 .. 6, a coarsest level below 8 x 8, an iters_host[l] outside
+ * 0 .. 64, their sum 0, scale not positive and finite, damping negative or not finite, min_corr < 6, jump outside (0, 1), fx, fy or
+ * baseline not positive and finite, cx or cy not finite, workspace_bytes below dis_disp_align_workspace(...), a misaligned workspace,
+ * maps wanted at a level that does not exist -> DIS_ERR_UNSUPPORTED. */
+typedef struct DisDispAlignDebug {
+  float *pyr, *maps;
+  double* sums;
+  int level;
+} DisDispAlignDebug;
+long dis_disp_align_workspace(int n, int tl, int h, int w, int levels);
+int dis_disp_align_poses(const float* disp, const float* K4_host, float baseline, int levels, const int* iters_host, float scale,
+                         float damping, int min_corr, float jump, float* R_pair, float* t_pair, float* stats,
+                         const DisDispAlignDebug* dbg, int n, int tl, int h, int w, void* workspace, long workspace_bytes, void* stream);
+
+/* dis_rigid_flow: the flow that disparities and poses imply (csrc/disp_align.hip) - flow.npz without an image-based estimator, for a
+ * static scene.  For track b, the ordered pair (i, j), i != j, and pixel (u, v) of frame i with a valid d (fp32, tests/disp_align_ref.py):
+ * P as in "track fusion" (z = fb / d, P = (z ((u - cx) / fx), z ((v - cy) / fy), z)), X_w = R_i^T (P - t_i), Y = R_j X_w + t_j in the
+ * operand orders given there; with Y2 > 0: u_j = (fx Y0) / Y2 + cx, v_j = (fy Y1) / Y2 + cy, flow = (u_j - u, v_j - v).  An invalid d
+ * or Y2 <= 0 writes zeros, as does the diagonal.  visible (optional, NULL: not wanted): 1 iff the flow was written,
+ * 0 <= u_j + 0.5 < w, 0 <= v_j + 0.5 < h, frame j's disparity d_j at (floor(u_j + 0.5), floor(v_j + 0.5)) is valid and
+ * |d_j - pred| <= tol pred with pred = fb / Y2; 0 on the diagonal.
+ * disp (n, tl, h, w), R (n, tl, 3, 3), t (n, tl, 3) (X_c = R X_w + t): DEVICE.  K4_host: HOST.  flow (n, tl tl, 2, h, w) - the layout of
+ * dis_dense_flow -, visible (n, tl tl, h, w) uint8: DEVICE, every element written.  One launch, a lane per pixel of a pair; capturable.
+ * Checks, in this order: NULL disp, R, t, K4_host or flow -> DIS_ERR_NULL; the extents of dis_track_poses -> DIS_ERR_BAD_SHAPE; tol not
+ * in (0, 1), fx, fy or baseline not positive and finite, cx or cy not finite -> DIS_ERR_UNSUPPORTED. */
+int dis_rigid_flow(const float* disp, const float* R, const float* t, const float* K4_host, float baseline, float tol, float* flow,
+                   unsigned char* visible, int n, int tl, int h, int w, void* stream);
+
 /* ---------------------------------------------------------------- volumetric fusion --------- */
 
 /* The per-frame disparity maps of ONE track -> a truncated signed distance volume on a regular lattice, and the volume -> an indexed
