@@ -13,6 +13,16 @@ def str2bool(v):
     raise argparse.ArgumentTypeError('Boolean value expected.')
 
 
+PSEUDO_GT_SOURCES = ('multi_frame', 'raycast_gt', 'raycast_sgm', 'raycast_single_frame', 'raycast_multi_frame')
+
+
+def pseudo_gt_stem(source):
+    """the file stem a --pseudo_gt_source names: multi_frame -> multi_frame_disp, raycast_X -> raycast_X"""
+    if source not in PSEUDO_GT_SOURCES:
+        raise ValueError(f'pseudo_gt_source is one of {PSEUDO_GT_SOURCES}, not {source!r}')
+    return 'multi_frame_disp' if source == 'multi_frame' else source
+
+
 def get_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--data_type', default='synthetic', choices=['synthetic', 'real'], type=str)
@@ -29,6 +39,13 @@ def get_parser():
     parser.add_argument('--architecture', help='The architecture which will be used', default='single_frame',
                         choices=['single_frame', 'multi_frame'], type=str)
     parser.add_argument('--use_pseudo_gt', help='Only applicable in single-frame model', default=False, type=str2bool)
+    # (not in the reference) which fused disparity the pseudo-GT term reads: multi_frame -> <track>/multi_frame_disp.npz (DIS-MF's
+    # output, the reference's), raycast_X -> <track>/raycast_X.npz (data/raycast.py --disp X), key `disp` in both.  A raycast map
+    # has holes (0): any value but the default pair (multi_frame, 0) selects the masked term, ops.masked_l1_multi
+    parser.add_argument('--pseudo_gt_source', help='Which fused disparity --use_pseudo_gt trains on (not in the reference)',
+                        default='multi_frame', choices=list(PSEUDO_GT_SOURCES), type=str)
+    parser.add_argument('--pseudo_gt_erode', help='Also leave out pixels within this many pixels of a hole of the pseudo ground '
+                        'truth (not in the reference)', default=0, choices=[0, 1, 2, 3], type=int)
     # (not in the reference) backward of the geometric loss: float atomics, or order-free sums that repeat bit for bit
     parser.add_argument('--geo_bwd', help='Backward of the geometric loss; default: the DIS_GEO_BWD environment variable, else atomic',
                         default=None, choices=['atomic', 'det'], type=str)

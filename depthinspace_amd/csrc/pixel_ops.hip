@@ -758,6 +758,167 @@ extern "C" int dis_sgm_l1_bwd(const float* out_disp, const float* sgm_disp, cons
   return DIS_OK;
 }
 
+// Masked multi-scale pseudo-GT term (include/dis_hip.h: dis_masked_l1_multi_fwd; tests/masked_l1_ref.py restates it): up to four
+// estimates against ONE target with holes, all in one launch.  A pixel counts when the target is > 0 over its whole (2r+1)^2 window
+// (clipped at the image, never leaving the plane).  No float atomics: block b leaves its n sums and its count in record 1 + b of
+// acc, the finalize launch adds the records in index order, and the grid depends on the shape alone - the same bits on every run.
+#define ML1_MAX 4
+#define ML1_REC (ML1_MAX + 1)  // doubles per record: sums of the estimates 0 .. 3, then the count of valid pixels
+#define ML1_BLOCKS 1024
+struct MaskedL1Est {
+  const float* o[ML1_MAX];
+};
+struct MaskedL1Grad {
+  float* g[ML1_MAX];
+};
+// (the window of a pixel is re-read through the cache: at r = 1 nine loads of which eight hit lines the neighbouring lanes and the
+// rows above and below have just brought in; no staging, the kernel stays a flat grid-stride loop like its neighbours in this file)
+__device__ __forceinline__ bool masked_l1_valid(const float* __restrict__ t, long i, float ti, int r, int x, int y, int h, int w) {
+  bool v = ti > 0.f;
+  if (r > 0) {
+    const int y0 = -min(r, y), y1 = min(r, h - 1 - y), x0 = -min(r, x), x1 = min(r, w - 1 - x);
+    for (int dy = y0; dy <= y1; ++dy) {
+      const float* row = t + i + (long)dy * w;
+      for (int dx = x0; dx <= x1; ++dx) v &= row[dx] > 0.f;
+    }
+  }
+  return v;
+}
+// the image coordinates of a thread's pixel, carried along its grid-stride loop: one division per thread, none per pixel
+struct MaskedL1Walk {
+  int x, y, dx, dy;
+};
+__device__ __forceinline__ MaskedL1Walk masked_l1_walk(long i0, long stride, int h, int w) {
+  const long row0 = i0 / w, drow = stride / w;
+  MaskedL1Walk k;
+  k.x = (int)(i0 - row0 * w), k.y = (int)(row0 % h);
+  k.dx = (int)(stride - drow * w), k.dy = (int)(drow % h);
+  return k;
+}
+__device__ __forceinline__ void masked_l1_step(MaskedL1Walk& k, int h, int w) {
+  k.x += k.dx, k.y += k.dy;  // (x, dx < w and y, dy < h: one carry and one wrap are enough)
+  if (k.x >= w) k.x -= w, ++k.y;
+  if (k.y >= h) k.y -= h;
+}
+template <int N>
+__global__ __launch_bounds__(256) void masked_l1_multi_sum_kernel(const MaskedL1Est est, const float* __restrict__ t,
+                                                                  double* __restrict__ acc, int r, int h, int w, long count) {
+  __shared__ double sm[4];
+  double s[N], c = 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) s[k] = 0.0;
+  const long i0 = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  MaskedL1Walk p = masked_l1_walk(i0, stride, h, w);
+  for (long i = i0; i < count; i += stride, masked_l1_step(p, h, w)) {
+    const float ti = t[i];
+    const bool v = masked_l1_valid(t, i, ti, r, p.x, p.y, h, w);
+    c += v ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const float d = fabsf(est.o[k][i] - ti);
+      s[k] += v ? (double)d : 0.0;  // (a select: whatever stands under a hole, NaN or inf included, adds nothing)
+    }
+  }
+  double* rec = acc + ML1_REC * (1 + (long)blockIdx.x);
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double b = block_sum_d(s[k], sm);
+    if (threadIdx.x == 0) rec[k] = b;
+  }
+  c = block_sum_d(c, sm);
+  if (threadIdx.x == 0) rec[ML1_MAX] = c;
+}
+// thread k adds column k of the records, and the counts, in index order; record 0 receives the totals (the backward reads the count).
+// The records are staged in LDS by the whole workgroup first, so that the serial walk does not wait for global memory per record.
+__global__ __launch_bounds__(256) void masked_l1_multi_finalize_kernel(double* __restrict__ acc, float* __restrict__ out, int n,
+                                                                       int nblocks) {
+  __shared__ double rec[ML1_REC * ML1_BLOCKS];
+  for (int j = threadIdx.x; j < ML1_REC * nblocks; j += 256) rec[j] = acc[ML1_REC + j];
+  __syncthreads();
+  const int k = threadIdx.x;
+  if (k >= n) return;
+  double s = 0.0, c = 0.0;
+  for (int b = 0; b < nblocks; ++b) {
+    s += rec[ML1_REC * b + k];
+    c += rec[ML1_REC * b + ML1_MAX];
+  }
+  acc[k] = s;
+  if (k == 0) acc[ML1_MAX] = c;
+  out[k] = c > 0.0 ? (float)(s / c) : 0.f;
+}
+template <int N>
+__global__ __launch_bounds__(256) void masked_l1_multi_bwd_kernel(const MaskedL1Est est, const float* __restrict__ t,
+                                                                  const double* __restrict__ acc, const float* __restrict__ gscale,
+                                                                  const MaskedL1Grad grad, int r, int h, int w, long count) {
+  const float cnt = (float)acc[ML1_MAX];
+  float g[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) g[k] = cnt > 0.f ? gscale[k] / cnt : 0.f;
+  const long i0 = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  MaskedL1Walk p = masked_l1_walk(i0, stride, h, w);
+  for (long i = i0; i < count; i += stride, masked_l1_step(p, h, w)) {
+    const float ti = t[i];
+    const bool v = masked_l1_valid(t, i, ti, r, p.x, p.y, h, w);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const float d = est.o[k][i] - ti;
+      grad.g[k][i] = v ? (d > 0.f ? g[k] : (d < 0.f ? -g[k] : 0.f)) : 0.f;
+    }
+  }
+}
+static int masked_l1_check(const float* const* ptrs, int n, int erode, int planes, int h, int w) {
+  if (planes <= 0 || h <= 0 || w <= 0 || n < 1 || n > ML1_MAX || erode < 0 || erode > 3) return DIS_ERR_BAD_SHAPE;
+  if ((long)h * w > 0x7fffffffL) return DIS_ERR_BAD_SHAPE;
+  for (int k = 0; k < n; ++k)
+    if (!ptrs[k]) return DIS_ERR_NULL;
+  return DIS_OK;
+}
+static inline int masked_l1_grid(long count) { return count < 256L * ML1_BLOCKS ? dis_cdiv(count, 256) : ML1_BLOCKS; }
+extern "C" long dis_masked_l1_multi_acc_doubles(void) { return ML1_REC * (1 + ML1_BLOCKS); }
+extern "C" int dis_masked_l1_multi_fwd(const float* const* est_host, int n, const float* target, int erode, double* acc, float* out,
+                                       int planes, int h, int w, void* stream) {
+  if (!est_host || !target || !acc || !out) return DIS_ERR_NULL;
+  const int rc = masked_l1_check(est_host, n, erode, planes, h, w);
+  if (rc != DIS_OK) return rc;
+  MaskedL1Est est = {};
+  for (int k = 0; k < n; ++k) est.o[k] = est_host[k];
+  const long count = (long)planes * h * w;
+  const int grid = masked_l1_grid(count);
+  hipStream_t s = (hipStream_t)stream;
+#define ML1_FWD(N) \
+  hipLaunchKernelGGL(masked_l1_multi_sum_kernel<N>, dim3(grid), dim3(256), 0, s, est, target, acc, erode, h, w, count)
+  if (n == 1) ML1_FWD(1);
+  else if (n == 2) ML1_FWD(2);
+  else if (n == 3) ML1_FWD(3);
+  else ML1_FWD(4);
+#undef ML1_FWD
+  hipLaunchKernelGGL(masked_l1_multi_finalize_kernel, dim3(1), dim3(256), 0, s, acc, out, n, grid);
+  DIS_CHECK_LAUNCH();
+  return DIS_OK;
+}
+extern "C" int dis_masked_l1_multi_bwd(const float* const* est_host, int n, const float* target, int erode, const double* acc,
+                                       const float* gscale, float* const* grad_host, int planes, int h, int w, void* stream) {
+  if (!est_host || !target || !acc || !gscale || !grad_host) return DIS_ERR_NULL;
+  int rc = masked_l1_check(est_host, n, erode, planes, h, w);
+  if (rc == DIS_OK) rc = masked_l1_check(grad_host, n, erode, planes, h, w);
+  if (rc != DIS_OK) return rc;
+  MaskedL1Est est = {};
+  MaskedL1Grad grad = {};
+  for (int k = 0; k < n; ++k) est.o[k] = est_host[k], grad.g[k] = grad_host[k];
+  const long count = (long)planes * h * w;
+  const int grid = dis_ew_grid(count, 256);
+  hipStream_t s = (hipStream_t)stream;
+#define ML1_BWD(N) \
+  hipLaunchKernelGGL(masked_l1_multi_bwd_kernel<N>, dim3(grid), dim3(256), 0, s, est, target, acc, gscale, grad, erode, h, w, count)
+  if (n == 1) ML1_BWD(1);
+  else if (n == 2) ML1_BWD(2);
+  else if (n == 3) ML1_BWD(3);
+  else ML1_BWD(4);
+#undef ML1_BWD
+  DIS_CHECK_LAUNCH();
+  return DIS_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Sobel-5 smoothness (reference model/networks.py:411-431, 693-731)
 // ------------------------------------------------------------------------------------------------

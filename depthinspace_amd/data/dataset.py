@@ -80,6 +80,13 @@ def write_synthetic_dataset(root, settings, n_samples, track_length=4, seed=1234
     return paths
 
 
+def pseudo_writer(stem, root='ROOT'):
+    """the command that writes <track>/<stem>.npz, the file a pseudo-GT stem names"""
+    if stem.startswith('raycast_'):
+        return f'`python -m depthinspace_amd.data.raycast {root} --disp {stem[len("raycast_"):]}`'
+    return 'data/presave_disp.py (DIS-MF)'
+
+
 class TrackNpzDataset(torch.utils.data.Dataset):
     """Mirror of the reference TrackSynDataset (data/dataset.py:36-125) on the .npz schema, restricted to the keys the
     hot path consumes (full-resolution scale only; the reference also loads three down-scaled copies that nothing on
@@ -87,7 +94,7 @@ class TrackNpzDataset(torch.utils.data.Dataset):
     testing is deterministic.  Augmentation (:128-186) is out of scope (host-side)."""
 
     def __init__(self, settings_path, sample_paths, track_length=4, train=True, data_aug=False, load_flow_data=False,
-                 load_primary_data=False, load_pseudo_gt=False, data_type='synthetic'):
+                 load_primary_data=False, load_pseudo_gt=False, data_type='synthetic', pseudo_stem='multi_frame_disp'):
         assert track_length <= 4
         self.settings = load_settings(os.path.dirname(settings_path) if settings_path.endswith('.npz') else settings_path)
         self.sample_paths = list(sample_paths)
@@ -96,6 +103,7 @@ class TrackNpzDataset(torch.utils.data.Dataset):
         self.load_flow_data = load_flow_data
         self.load_primary_data = load_primary_data
         self.load_pseudo_gt = load_pseudo_gt
+        self.pseudo_stem = pseudo_stem   # pseudo_gt is the `disp` of <track>/<pseudo_stem>.npz: multi_frame_disp, or raycast_<disp>
         self.data_type = data_type
         s = self.settings
         self.imsizes = [(s.imsize[0] // (2 ** k), s.imsize[1] // (2 ** k)) for k in range(4)]
@@ -133,6 +141,10 @@ class TrackNpzDataset(torch.utils.data.Dataset):
             with np.load(os.path.join(p, 'single_frame_disp.npz')) as f:
                 ret['primary_disp'] = np.stack([f['disp'][t] for t in track], 0)
         if self.load_pseudo_gt:
-            with np.load(os.path.join(p, 'multi_frame_disp.npz')) as f:
+            path = os.path.join(p, self.pseudo_stem + '.npz')
+            if not os.path.exists(path):
+                raise FileNotFoundError(f'{path} is missing: {pseudo_writer(self.pseudo_stem, os.path.dirname(os.path.normpath(p)))} '
+                                        f'writes it')
+            with np.load(path) as f:
                 ret['pseudo_gt'] = np.stack([f['disp'][t] for t in track], 0)
         return {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)) for k, v in ret.items()}

@@ -5,11 +5,12 @@ arrays, bit for bit, as one raw little-endian fp32 file:
     frames.f32                im (4,H,W) | ambient (4,H,W) | disp (4,H,W) | [sgm_disp (4,H,W)] | R (4,3,3) | t (4,3)
     flow.f32                  flow_ij (2,H,W) in the order 01 02 03 10 12 13 20 21 23 30 31 32
     single_frame_disp.f32     disp (4,H,W)          multi_frame_disp.f32      disp (4,H,W)
+    raycast_<disp>.f32        disp (4,H,W) of raycast_<disp>.npz, where a track holds one (a pseudo-GT source; normal and value are not packed)
 (`grad` is not stored: nothing reads it.  R and t come last, so the image planes stay 16-byte aligned when H*W % 4 == 0.)
 <root>/packed.json holds the version, imsize and the field list of frames.f32; its presence selects this path in Worker._loader.
 
-A *record* is what one stage reads of one track: frames | flow | single_frame_disp (if the stage loads it) | multi_frame_disp (if
-pseudo-GT).  record_layout() is the one place that knows the offsets: the packer, the loader and ops.assemble_tracks use it.
+A *record* is what one stage reads of one track: frames | flow | single_frame_disp (if the stage loads it) | multi_frame_disp, or the
+raycast file the stage names instead (if pseudo-GT).  record_layout() is the one place that knows the offsets: the packer, the loader and ops.assemble_tracks use it.
 
 PackedTrackLoader reads the records with a thread pool (file reads release the GIL: no worker processes, no pickling) straight into
 a pinned staging ring, uploads each batch with ONE copy on its own stream while the previous step runs, and hands out PackedBatch
@@ -25,9 +26,13 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
+from .trackfiles import SOURCES
+
 VERSION = 1
 PAIRS = tuple(f'{i}{j}' for i in range(4) for j in range(4) if i != j)   # file order of the flows: pair(p, q) = 3p + q - (q > p)
 FILES = ('frames', 'flow', 'single_frame_disp', 'multi_frame_disp')
+# pseudo-GT of another stem (data/raycast.py writes them; only `disp` is packed): packed where a track holds the .npz
+RAYCAST_FILES = tuple(f'raycast_{s}' for s in SOURCES)
 
 
 def pack_command(root):
@@ -43,9 +48,12 @@ class AssembledBatch(dict):
     its tensors as they are"""
 
 
-def record_layout(h, w, has_sgm=False, primary=False, pseudo=False):
+def record_layout(h, w, has_sgm=False, primary=False, pseudo=False, pseudo_stem='multi_frame_disp'):
     """float offsets of every field of a record (keys: the field names of DisTrackLayout), plus
-    'size' (floats per record) and 'files': ((file stem, float offset, floats), ...) in record order."""
+    'size' (floats per record) and 'files': ((file stem, float offset, floats), ...) in record order.  pseudo_stem: the file the
+    pseudo_gt plane is read from (multi_frame_disp, or one of RAYCAST_FILES); sizes and offsets do not depend on it."""
+    if pseudo_stem != 'multi_frame_disp' and pseudo_stem not in RAYCAST_FILES:
+        raise ValueError(f'pseudo_stem is multi_frame_disp or one of {RAYCAST_FILES}, not {pseudo_stem!r}')
     hw = int(h) * int(w)
     lay, off = {}, 0
     for name in ('im', 'ambient', 'disp') + (('sgm_disp',) if has_sgm else ()):
@@ -58,7 +66,7 @@ def record_layout(h, w, has_sgm=False, primary=False, pseudo=False):
     lay['flow'] = off
     files.append(('flow', off, 24 * hw))
     off += 24 * hw
-    for on, name, stem in ((primary, 'primary_disp', 'single_frame_disp'), (pseudo, 'pseudo_gt', 'multi_frame_disp')):
+    for on, name, stem in ((primary, 'primary_disp', 'single_frame_disp'), (pseudo, 'pseudo_gt', pseudo_stem)):
         if on:
             lay[name] = off
             files.append((stem, off, 4 * hw))
@@ -120,7 +128,7 @@ def pack_dataset(root):
         h, w = (int(v) for v in f['im'].shape[-2:])
     written = []
     for d in dirs:
-        for stem in FILES:
+        for stem in FILES + RAYCAST_FILES:
             src, dst = os.path.join(d, stem + '.npz'), os.path.join(d, stem + '.f32')
             if not os.path.exists(src) or not is_stale(dst, src):
                 continue
@@ -219,7 +227,7 @@ class PackedTrackLoader(object):
 
     def __init__(self, sample_paths, order, batch_size, track_length, train, imsize, has_sgm=False, primary=False, pseudo=False,
                  want_sgm=None, drop_last=False, num_threads=4, seed=0, device=None, depth=2, reader=None, event_factory=None,
-                 root=None):
+                 root=None, pseudo_stem='multi_frame_disp'):
         assert 1 <= track_length <= 4 and batch_size >= 1 and depth >= 2
         self.sample_paths = list(sample_paths)
         self.order = [int(i) for i in order]
@@ -235,7 +243,8 @@ class PackedTrackLoader(object):
         self.depth = int(depth)
         self.reader = reader or read_exact
         self.root = root if root is not None else (os.path.dirname(self.sample_paths[0]) if self.sample_paths else '.')
-        self.layout = record_layout(self.imsize[0], self.imsize[1], self.has_sgm, self.primary, self.pseudo)
+        self.pseudo_stem = pseudo_stem
+        self.layout = record_layout(self.imsize[0], self.imsize[1], self.has_sgm, self.primary, self.pseudo, pseudo_stem)
         self.record = self.layout['size']
         self.device = torch.device(device) if device is not None else None
         if self.device is not None and self.device.type != 'cuda':
@@ -272,7 +281,10 @@ class PackedTrackLoader(object):
                     raise PackedDataError(f'{f32} is missing or older than {stem}.npz')
                 self.reader(f32, self._host_bytes[slot][base + off * 4: base + (off + count) * 4])
             except FileNotFoundError as e:
-                raise PackedDataError(f'{f32} is missing: run `{pack_command(self.root)}`') from e
+                first = ''
+                if stem in RAYCAST_FILES and not os.path.exists(npz):   # (no .npz to pack either: name what writes it)
+                    first = f'`python -m depthinspace_amd.data.raycast {self.root} --disp {stem[len("raycast_"):]}`, then '
+                raise PackedDataError(f'{f32} is missing: run {first}`{pack_command(self.root)}`') from e
             except PackedDataError as e:
                 if 'run `' in str(e):
                     raise
@@ -364,7 +376,8 @@ def loader_for(dset, order, batch_size, train, num_threads, seed, device, root):
     return PackedTrackLoader(dset.sample_paths, order, batch_size, dset.track_length, train, imsize,
                              has_sgm='sgm_disp' in meta['frames_fields'], primary=dset.load_primary_data,
                              pseudo=dset.load_pseudo_gt, want_sgm=dset.data_type == 'real', drop_last=train,
-                             num_threads=num_threads, seed=seed, device=device, root=root)
+                             num_threads=num_threads, seed=seed, device=device, root=root,
+                             pseudo_stem=getattr(dset, 'pseudo_stem', 'multi_frame_disp'))
 
 
 if __name__ == '__main__':

@@ -29,6 +29,9 @@ SIGS = {
     'dis_l1_mean_bwd': 'pppplp',
     'dis_sgm_l1_fwd': 'pppfpplp',
     'dis_sgm_l1_bwd': 'pppfppplp',
+    'dis_masked_l1_multi_acc_doubles': '',
+    'dis_masked_l1_multi_fwd': 'pipippiiip',
+    'dis_masked_l1_multi_bwd': 'pipipppiiip',
     'dis_smooth_loss_fwd': 'ppppiiip',
     'dis_smooth_loss_bwd': 'pppppiiip',
     'dis_disp_to_depth_fwd': 'ppflp',
@@ -189,7 +192,7 @@ SIGS = {
     'dis_allreduce_destroy': 'p',
 }
 _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_workspace', 'dis_conv2d_bwd_fused_c16_workspace', 'dis_conv2d_bwd_fused_c16_slots', 'dis_conv2d_bwd_fused_bf16x3_workspace', 'dis_convb_pack_desc_bytes', 'dis_convg_splitk_workspace', 'dis_convb_splitk_workspace', 'dis_conv2d_gnsums_slots', 'dis_conv2d_wgrad_workspace', 'dis_convg_pack_workspace', 'dis_convg_wgrad_workspace',
-             'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
+             'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_masked_l1_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace', 'dis_geo_loss_bwd_det_workspace',
              'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace',
              'dis_pose_joint_workspace', 'dis_disp_align_workspace',

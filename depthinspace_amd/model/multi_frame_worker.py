@@ -32,7 +32,7 @@ class Worker(worker.Worker):
             from ..data.dataset import TrackNpzDataset
             return TrackNpzDataset(self.settings_path, paths, track_length=self.track_length, train=train, data_aug=train,
                                    load_flow_data=True, load_primary_data=self.load_primary_data, load_pseudo_gt=pseudo,
-                                   data_type=self.data_type)
+                                   data_type=self.data_type, pseudo_stem=self.pseudo_gt_stem)
         from ..data.dataset import SyntheticTrackDataset
         return SyntheticTrackDataset(self.settings, n_synth, self.track_length, seed=seed,
                                      load_primary_data=self.load_primary_data, load_pseudo_gt=pseudo)

@@ -73,9 +73,14 @@ class Worker(multi_frame_worker.Worker):
                                        accs=(accs[tidx0], accs[tidx1]) if accs is not None else None)
                 vals.append((val, 0.2 / ge_num))
         # pseudo ground truth (DIS-FTSF)
-        if self.use_pseudo_gt:
+        if self.use_pseudo_gt and self.pseudo_gt_source == 'multi_frame' and self.pseudo_gt_erode == 0:
             for s, o in zip(itertools.count(), out):
                 vals.append((ops.l1_mean(o, self.data['pseudo_gt']), 0.1 / (2 ** s)))
+        elif self.use_pseudo_gt:
+            # a target with holes (a raycast map is 0 where no ray met the surface), or one whose hole borders are left out: only
+            # its valid pixels count, all scales in one launch each way
+            for s, val in enumerate(ops.masked_l1_multi(out, self.data['pseudo_gt'], self.pseudo_gt_erode)):
+                vals.append((val, 0.1 / (2 ** s)))
         if train and self.data_type == 'real' and self.current_epoch < self.warmup_epochs:
             for s, o in zip(itertools.count(), out):  # every scale, a fresh noise draw each (reference :158-163)
                 vals.append((self.sgm_warmup_term(o, s), 0.1))

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import networks
+from ..co.args import pseudo_gt_stem
 from .multi_frame_networks import FlowDict
 
 
@@ -94,6 +95,13 @@ class Worker(object):
                  test_device=None, max_train_iter=-1, settings=None, output_dir=None, data_root=None, use_graph=None,
                  geo_bwd=None):
         self.use_pseudo_gt = args.use_pseudo_gt
+        # which fused disparity the pseudo-GT term reads and how far it stays away from that map's holes (co/args.py; a Namespace
+        # without the fields means the reference's: DIS-MF's output, every pixel)
+        self.pseudo_gt_source = getattr(args, 'pseudo_gt_source', 'multi_frame')
+        self.pseudo_gt_erode = int(getattr(args, 'pseudo_gt_erode', 0))
+        self.pseudo_gt_stem = pseudo_gt_stem(self.pseudo_gt_source)
+        if not 0 <= self.pseudo_gt_erode <= 3:
+            raise ValueError(f'pseudo_gt_erode is 0 .. 3, not {self.pseudo_gt_erode}')
         self.lcn_radius = args.lcn_radius
         self.track_length = args.track_length
         self.data_type = args.data_type

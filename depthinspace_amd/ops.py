@@ -898,6 +898,60 @@ def sgm_l1(o, sgm_disp, noise, thresh=30.0):
     return _SgmL1.apply(o, sgm_disp, noise, thresh)
 
 
+def _ptr_table(tensors):
+    """a host array of the tensors' device addresses (the entry point copies them into its kernel arguments)"""
+    return (_ct.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _MaskedL1Multi(torch.autograd.Function):
+    """[masked mean |o - target| for o in outs] as ONE autograd node: one accumulate and one finalize launch forward, one launch
+    backward (dis_masked_l1_multi_fwd / _bwd), whatever the number of estimates.  A pixel counts when target > 0 over its whole
+    (2 erode + 1)^2 window; the count is shared by the estimates and stays on the device (no valid pixel: values and gradients 0)."""
+
+    @staticmethod
+    def forward(ctx, target, erode, *outs):
+        target = _c(target)
+        outs = [_c(o) for o in outs]
+        _chk(target, *outs)
+        n = len(outs)
+        if not 1 <= n <= 4:
+            raise RuntimeError(f'masked_l1_multi: 1 .. 4 estimates, not {n}')
+        if int(erode) != erode or not 0 <= erode <= 3:
+            raise RuntimeError(f'masked_l1_multi: erode is an integer in 0 .. 3, not {erode!r}')
+        shape = tuple(target.shape)
+        if len(shape) not in (4, 5) or shape[-3] != 1:
+            raise RuntimeError(f'masked_l1_multi: target of shape {shape}: (tl, bs, 1, H, W) or (N, 1, H, W) is expected')
+        if any(tuple(o.shape) != shape for o in outs):
+            raise RuntimeError(f'masked_l1_multi: estimates of shapes {[tuple(o.shape) for o in outs]} against a target of {shape}')
+        h, w = shape[-2:]
+        planes = target.numel() // (h * w) if h * w else 0
+        acc = torch.empty(lib.fn('dis_masked_l1_multi_acc_doubles')(), dtype=torch.float64, device=target.device)
+        vals = torch.empty(n, dtype=torch.float32, device=target.device)
+        lib.call('dis_masked_l1_multi_fwd', _ptr_table(outs), n, target, int(erode), acc, vals, planes, h, w)
+        ctx.save_for_backward(target, acc, *outs)
+        ctx.cfg = (int(erode), planes, h, w)
+        return tuple(vals[k] for k in range(n))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        target, acc = ctx.saved_tensors[:2]
+        outs = ctx.saved_tensors[2:]
+        erode, planes, h, w = ctx.cfg
+        zero = None
+        if any(g is None for g in gs):
+            zero = torch.zeros((), dtype=torch.float32, device=target.device)
+        gscale = torch.stack([g.reshape(()).float() if g is not None else zero for g in gs])
+        grads = [torch.empty_like(o) for o in outs]
+        lib.call('dis_masked_l1_multi_bwd', _ptr_table(outs), len(outs), target, erode, acc, gscale, _ptr_table(grads), planes, h, w)
+        return (None, None) + tuple(grads)
+
+
+def masked_l1_multi(outs, target, erode=0):
+    """per-estimate sum(|o - target| over valid) / count(valid) (a list of device scalars), valid = target > 0 over the whole
+    (2 erode + 1)^2 window inside the image: the pseudo-GT term on a target with holes (<track>/raycast_<disp>.npz)"""
+    return list(_MaskedL1Multi.apply(target, erode, *outs))
+
+
 class _SmoothLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, disp, amb):

@@ -102,6 +102,24 @@ int dis_sgm_l1_fwd(const float* out_disp, const float* sgm_disp, const float* no
 int dis_sgm_l1_bwd(const float* out_disp, const float* sgm_disp, const float* noise, float thresh, const double* acc,
                    const float* gscale, float* grad_out_disp, long count, void* stream);
 
+/* Masked multi-scale pseudo-GT term (DIS-FTSF on a target with holes, e.g. <track>/raycast_<disp>.npz): n = 1 .. 4 estimates against
+ * ONE target, all float32, contiguous, seen as (planes, h, w); est_host / grad_host: HOST arrays of n device pointers (copied into
+ * the kernel arguments by value: a captured call holds them).  erode = r in 0 .. 3.
+ *   valid(p, y, x)  target > 0 at every pixel of the (2r+1)^2 window around (y, x) that lies inside the image, in plane p (pixels
+ *                   outside the image do not invalidate; NaN is not > 0: a hole)
+ *   out[s]          (float)(sum over valid of (double)|est_s - target| / (double)N), N = valid pixels of the whole call; 0 when N = 0
+ *   grad_s[i]       valid_i ? sign(est_s[i] - target[i]) * (gscale[s] / (float)N) : 0   (sign(0) = 0; all 0 when N = 0)
+ * Masking is a select: a non-finite estimate or target under a hole contributes nothing.  acc: dis_masked_l1_multi_acc_doubles()
+ * doubles of scratch (no zeroing), kept for the backward, which reads N from it: record 0 = {sum_0 .. sum_3, N}, behind it one such
+ * record per workgroup, added in index order by a second launch - no atomics, the grid depends on the shape alone, so out and grad
+ * have the same bits on every run.  Forward: two launches, backward: one, for any n; nothing is read back to the host.
+ * gscale: n device floats.  tests/masked_l1_ref.py restates the arithmetic in numpy. */
+long dis_masked_l1_multi_acc_doubles(void);
+int dis_masked_l1_multi_fwd(const float* const* est_host, int n, const float* target, int erode, double* acc, float* out, int planes,
+                            int h, int w, void* stream);
+int dis_masked_l1_multi_bwd(const float* const* est_host, int n, const float* target, int erode, const double* acc,
+                            const float* gscale, float* const* grad_host, int planes, int h, int w, void* stream);
+
 /* DisparitySmoothLoss, reference model/networks.py:411-431 with SobelFilter(ksize=5) :693-731.
  * disp, amb: (n,1,h,w).  acc: 1 zeroed double; out: 1 float = mean over (n,2,h,w). */
 int dis_smooth_loss_fwd(const float* disp, const float* amb, double* acc, float* out, int n, int h, int w,
