@@ -7,6 +7,13 @@ array from the authors' real dataset and has no code that produces it.  Semi-glo
 structured-light depth: --report compares it with the stored ground truth through co/metric.py.
 
     python -m depthinspace_amd.data.presave_sgm ROOT [--ndisp N] [--p1 P1] [--p2 P2] [--uniq U] [--lr L] [--report] [--pack]
+                                                     [--speckle N [--speckle-diff D] [--refilter]]
+
+--speckle N (default 0: off, and then no byte of any file differs) runs the speckle filter ops.speckle_filter on the matcher's output
+before it is stored: every 4-connected region of at most N pixels whose neighbouring disparities differ by at most D (--speckle-diff,
+default 1.0) is set to 0 (include/dis_hip.h, section "speckle filter").  --refilter applies the same filter to the sgm_disp a track
+already stores, in place; the filter is idempotent, so a second run changes nothing.  --report reads what is stored and so shows the
+effect.
 
 Known limit: the workers mask the warm-up term with sgm_disp > 30 (the reference's constant).  With the default synthetic geometry
 (fx * baseline about 10.7) every rendered disparity is below 30, so the term sees no pixel there; it does with a geometry whose near
@@ -34,6 +41,14 @@ def match_frames(im, pattern, ndisp=64, p1=7, p2=60, uniq=5, lr=1, device='cuda'
     return d.cpu().numpy()
 
 
+def filter_speckles(sgm, max_size, max_diff=1.0, device='cuda'):
+    """sgm (4, 1, H, W) float32 numpy -> the same with every region of at most max_size pixels set to 0 (ops.speckle_filter on the
+    device)"""
+    from .. import ops
+    d = ops.speckle_filter(torch.from_numpy(np.ascontiguousarray(sgm, dtype=np.float32)).to(torch.device(device)), max_size, max_diff)
+    return d.cpu().numpy()
+
+
 def sgm_report(data_root):
     """co/metric.py's DistanceMetric and OutlierFractionMetric of sgm_disp against disp over the pixels where the match is valid
     (sgm_disp != 0) and the surface was seen (disp > 0), over every track of data_root, plus `valid`: the fraction of the seen pixels
@@ -55,20 +70,36 @@ def sgm_report(data_root):
     return res
 
 
-def presave_sgm(data_root, ndisp=64, p1=7, p2=60, uniq=5, lr=1, report=False, pack=False, device='cuda'):
+def presave_sgm(data_root, ndisp=64, p1=7, p2=60, uniq=5, lr=1, report=False, pack=False, device='cuda', speckle=0, speckle_diff=1.0,
+                refilter=False):
     """Adds sgm_disp (4, 1, H, W) to the frames.npz of every track directory of data_root that has none (incremental; the other arrays
-    stay byte-identical; each file is replaced atomically).  pack: re-runs packed.pack_dataset.  Returns the number of tracks matched,
-    or with report=True the dict of sgm_report (printed as one line)."""
+    stay byte-identical; each file is replaced atomically).  speckle > 0: the new array goes through filter_speckles(sgm, speckle,
+    speckle_diff) first; refilter: a track that already has sgm_disp gets that array filtered in place (a file the filter does not
+    change is not rewritten).  pack: re-runs packed.pack_dataset.  Returns the number of tracks written, or with report=True the dict of
+    sgm_report (printed as one line)."""
     data_root = str(data_root)
+    speckle, speckle_diff = int(speckle), float(speckle_diff)
+    if speckle < 0 or not 0 <= speckle_diff < float('inf'):
+        raise ValueError('--speckle is a pixel count >= 0 and --speckle-diff a finite disparity difference >= 0')
+    if refilter and speckle == 0:
+        raise ValueError('--refilter needs --speckle N with N > 0')
     pattern = np.ascontiguousarray(load_settings(data_root).pattern[..., 0], dtype=np.float32)
     done = 0
     for d in packed.track_dirs(data_root):
         path = os.path.join(d, 'frames.npz')
         with np.load(path) as f:
-            if 'sgm_disp' in f.files:
+            if 'sgm_disp' in f.files and not refilter:
                 continue
-            im = f['im']
-        sgm = np.asarray(match_frames(im, pattern, ndisp, p1, p2, uniq, lr, device), dtype=np.float32).reshape(im.shape)
+            stored = f['sgm_disp'] if 'sgm_disp' in f.files else None
+            im = f['im'] if stored is None else None
+        if stored is None:
+            sgm = np.asarray(match_frames(im, pattern, ndisp, p1, p2, uniq, lr, device), dtype=np.float32).reshape(im.shape)
+        else:
+            sgm = stored
+        if speckle > 0:
+            sgm = np.asarray(filter_speckles(sgm, speckle, speckle_diff, device), dtype=np.float32).reshape(sgm.shape)
+            if stored is not None and sgm.dtype == stored.dtype and sgm.tobytes() == stored.tobytes():
+                continue
         rewrite_npz(path, {'sgm_disp': sgm})
         done += 1
     if pack:
@@ -92,10 +123,15 @@ def main(argv=None):
     ap.add_argument('--lr', type=int, default=1, help='left-right tolerance in pixels')
     ap.add_argument('--report', action='store_true', help='print co/metric.py numbers of sgm_disp against disp')
     ap.add_argument('--pack', action='store_true', help='also (re)write the packed files (data/packed.py)')
+    ap.add_argument('--speckle', type=int, default=0, metavar='N',
+                    help='set regions of at most N pixels of similar disparity to 0 before storing (0: off)')
+    ap.add_argument('--speckle-diff', type=float, default=1.0, metavar='D', help='largest disparity step inside a region')
+    ap.add_argument('--refilter', action='store_true', help='also filter the sgm_disp that tracks already store (needs --speckle)')
     a = ap.parse_args(argv)
-    r = presave_sgm(a.root, a.ndisp, a.p1, a.p2, a.uniq, a.lr, report=a.report, pack=a.pack)
+    r = presave_sgm(a.root, a.ndisp, a.p1, a.p2, a.uniq, a.lr, report=a.report, pack=a.pack, speckle=a.speckle,
+                    speckle_diff=a.speckle_diff, refilter=a.refilter)
     if not a.report:
-        print(f'{r} tracks matched under {a.root}')
+        print(f'{r} tracks {"written" if a.refilter else "matched"} under {a.root}')
 
 
 if __name__ == '__main__':

@@ -2763,6 +2763,35 @@ def sgm_disparity(im, pattern, ndisp=64, p1=7, p2=60, uniq=5, lr=1, want_debug=F
     return (disp, dbg) if want_debug else disp
 
 
+def speckle_filter(disp, max_size=100, max_diff=1.0, want_debug=False, workspace=None):
+    """dis_speckle_filter: the disparity maps disp (n, 1, H, W) or (n, H, W) with every 4-connected component of similar disparity of at
+    most max_size pixels set to 0 -> a new tensor with the shape of disp (include/dis_hip.h, section "speckle filter"; tests/speckle_ref.py
+    restates it in numpy and the kernels equal it bit for bit).  Valid pixels are 0 < d < inf; neighbours are linked when both are valid
+    and |d_p - d_q| <= max_diff in fp32; max_size >= 0 (0 keeps every valid pixel), max_diff >= 0 and finite.  want_debug: also a dict
+    with label (n, H, W) int32 (y W + x of the component's first pixel, -1: invalid) and size (n, H, W) int32 (its pixel count, 0: invalid).
+    The input is data: no autograd.  Four launches on the current stream; workspace: an optional uint8 tensor of at least
+    dis_speckle_workspace(...) bytes to reuse between calls (and what makes the call capturable without an allocation)."""
+    _chk(disp)
+    if not (disp.dim() == 3 or (disp.dim() == 4 and disp.shape[1] == 1)):
+        raise RuntimeError('speckle_filter: disp (n, 1, H, W) or (n, H, W) is expected')
+    n, h, w = int(disp.shape[0]), int(disp.shape[-2]), int(disp.shape[-1])
+    max_size, max_diff = int(max_size), float(max_diff)
+    need = lib.fn('dis_speckle_workspace')(n, h, w)
+    if need < 0:
+        raise lib.DisHipError(f'dis_speckle_workspace: unsupported extents n={n} h={h} w={w}')
+    if not (0 <= max_size <= 0x7fffffff and 0 <= max_diff <= 3.4028234663852886e38):   # refused before anything is allocated or launched
+        raise lib.DisHipError(f'speckle_filter: unsupported configuration max_size={max_size} max_diff={max_diff}')
+    dev = disp.device
+    workspace = _workspace('speckle_filter', need, workspace, dev)
+    out = torch.empty_like(disp)
+    dbg = None
+    if want_debug:
+        dbg = {'label': torch.empty((n, h, w), dtype=torch.int32, device=dev),
+               'size': torch.empty((n, h, w), dtype=torch.int32, device=dev)}
+    lib.call('dis_speckle_filter', disp, out, dbg and dbg['label'], dbg and dbg['size'], n, h, w, max_size, max_diff, workspace)
+    return (out, dbg) if want_debug else out
+
+
 def flow_level_sizes(h, w, min_size=8):
     """[(h_0, w_0), (h_1, w_1), ...] of dis_dense_flow's pyramid: a further level while min(h, w) >= 2 min_size at the coarsest; every
     level halves the one before, rounding up"""

@@ -855,6 +855,29 @@ long dis_sgm_workspace(int n, int h, int w, int ndisp);
 int dis_sgm_disparity(const float* im, const float* pattern, float* disp, int* d_int, short* vol, long long* census, int n, int h, int w,
                       int ndisp, int p1, int p2, int uniq, int lr, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- speckle filter ------------ */
+
+/* Region-level post-filter of a disparity map (csrc/speckle.hip), the step classical pipelines run after the matcher's own checks: the
+ * 4-connected components of similar disparity are labelled and the small ones are invalidated.  tests/speckle_ref.py restates it in
+ * numpy and the kernels match it bit for bit.
+ *   valid      0 < d < inf; NaN, +-inf, 0 and negative values are invalid.
+ *   linked     two 4-neighbours of the same image, both valid, with fabsf(d_p - d_q) <= max_diff (the difference in fp32).
+ *   component  a class of the transitive closure of `linked`: a ramp of max_diff per pixel is one component.
+ *   out        the bits of disp where the pixel is valid and its component has MORE than max_size pixels, else 0.0f.  max_size 0 keeps
+ *              every valid pixel; max_size >= h w empties the map.  Removing a component changes no other: the filter is idempotent.
+ * disp, out (n, h, w): DEVICE; every element of out is written; out must not alias disp.  Optional outputs (NULL: not wanted): label
+ * (n, h, w) int32 = y w + x of the component's first pixel in row order inside its image, -1 for an invalid pixel; size (n, h, w)
+ * int32 = the pixels of the component, 0 for an invalid pixel.
+ * workspace: dis_speckle_workspace(n, h, w) BYTES (-1: unsupported extents), 16-byte aligned, no initialisation: every word that is
+ * counted into is written first.  Four launches (three when the image is a single tile of 64 x 16), no allocation, no synchronisation:
+ * capturable.  The only atomics are integer minima and integer adds whose results do not depend on the order: two calls on the same
+ * input give the same bits.
+ * Checks, in this order: NULL disp, out or workspace -> DIS_ERR_NULL; n, h, w <= 0, h or w > 8192, n h w >= 2^31 -> DIS_ERR_BAD_SHAPE;
+ * max_size < 0, max_diff negative, NaN or infinite, a misaligned workspace -> DIS_ERR_UNSUPPORTED. */
+long dis_speckle_workspace(int n, int h, int w);
+int dis_speckle_filter(const float* disp, float* out, int* label, int* size, int n, int h, int w, int max_size, float max_diff,
+                       void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- dense optical flow -------- */
 
 /* flow_ij for every ordered pair of frames of a track (csrc/flow.hip): what the multi-frame stage reads from flow.npz, for tracks that
