@@ -153,6 +153,10 @@ __device__ __forceinline__ Lerp resize_src(int dst, float scale, int in, int ali
 // sums the four taps as fma(d, w11, fma(c, w10, fma(a, w00, b * w01))); the generic one nests
 // fma(top, ly0, bot * ly1) with top = fma(a, lx0, b * lx1).  (tests/bitexact.py restates both and is checked against
 // torch bit for bit.)  a,b = row i0 at columns i0,i1;  c,d = row i1.
+// The bit-for-bit claim holds, and is tested, for align_corners=True only.  With align_corners=False torch rounds the source
+// position differently from resize_src at some columns (one ulp of src: 13 x 67 -> 21 x 100, columns 24 and 48, values apart by
+// about 4e-6): those resizes feed value-class outputs (the single-frame disparities) and are held to a per-element bound against
+// float64 instead (tests/test_resize_exact_gpu.py).
 __device__ __forceinline__ float bilerp_aten(float a, float b, float c, float d, const Lerp& Ly, const Lerp& Lx,
                                              bool small) {
   if (small) {

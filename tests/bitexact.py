@@ -69,7 +69,7 @@ def lerp_idx(nin, nout):
     if nin == nout:
         i = np.arange(nout)
         return i, i, np.ones(nout, f32), np.zeros(nout, f32)
-    scale = f32(nin - 1) / f32(nout - 1)
+    scale = f32(nin - 1) / f32(nout - 1) if nout > 1 else f32(0)   # (area_pixel_compute_scale: 0 for a single output index)
     src = (scale * np.arange(nout, dtype=f32)).astype(f32)
     i0 = np.minimum(np.floor(src).astype(np.int64), nin - 1)
     i1 = np.minimum(i0 + 1, nin - 1)

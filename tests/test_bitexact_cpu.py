@@ -9,6 +9,7 @@ import torch
 from oracle import dis_oracle as O
 from depthinspace_amd import synth
 from tests import bitexact as B
+from tests import resize_ref as RR
 
 
 def _inputs(H, W, bs, seed, rnd, **kw):
@@ -66,6 +67,21 @@ def test_geometry_keys_and_topk_bit_exact(cfg):
             okey = tap['key'].numpy()
             assert eq(np.where(valid > 0, dist, okey.max()).astype(np.float32), okey)   # keys, bit for bit
             assert eq(sel[ti], tap['idx'].numpy())                                      # torch.topk's ids, in its order
+
+
+@pytest.mark.parametrize('shape', RR.ATEN_AC)
+def test_resize_ac_bit_exact_beyond_2x_down(shape):
+    """B.resize_ac equals F.interpolate(align_corners=True) bit for bit at the shapes tests/test_resize_exact_gpu.py compares the
+    planar resize and mf_geometry_resize with it at: up and down sampling at non-integer ratios, equal sizes, a single output
+    pixel (scale 0) and out_h + out_w > 128 (ATen's generic kernel)"""
+    hin, win, ho, wo = shape
+    g = torch.Generator().manual_seed(hin * 100 + wo)
+    x = torch.randn(2, 3, hin, win, generator=g)
+    y = torch.nn.functional.interpolate(x, size=(ho, wo), mode='bilinear', align_corners=True)
+    assert np.array_equal(B.resize_ac(x.numpy(), ho, wo), y.numpy())
+    m = (torch.rand(2, 3, hin, win, generator=g) > 0.3).float()
+    ym = torch.nn.functional.interpolate(m, size=(ho, wo), mode='bilinear', align_corners=True)
+    assert np.array_equal(B.resize_ac(m.numpy(), ho, wo), ym.numpy())
 
 
 @pytest.mark.parametrize('cfg', [(48, 56, 2, 3, True), (64, 64, 1, 1234, False)])
