@@ -170,6 +170,8 @@ SIGS = {
     'dis_sgm_disparity': 'pppppp' + 'iiiiiiii' + 'pp',
     'dis_speckle_workspace': 'iii',
     'dis_speckle_filter': 'pppp' + 'iiii' + 'f' + 'pp',
+    'dis_disp_densify_workspace': 'iii',
+    'dis_disp_densify': 'ppp' + 'iiiii' + 'f' + 'i' + 'pp',
     'dis_flow_workspace': 'iiiii',
     'dis_dense_flow': 'ppp' + 'iiii' + 'f' + 'iii' + 'pp',
     'dis_fuse_workspace': 'iiii',
@@ -196,7 +198,7 @@ SIGS = {
 _RET_LONG = {'dis_conv2d_bwd_fused_workspace', 'dis_conv2d_bwd1x1_scaled_gnb_workspace', 'dis_conv2d_bwd_fused_c16_workspace', 'dis_conv2d_bwd_fused_c16_slots', 'dis_conv2d_bwd_fused_bf16x3_workspace', 'dis_convb_pack_desc_bytes', 'dis_convg_splitk_workspace', 'dis_convb_splitk_workspace', 'dis_conv2d_gnsums_slots', 'dis_conv2d_wgrad_workspace', 'dis_convg_pack_workspace', 'dis_convg_wgrad_workspace',
              'dis_colsum_workspace', 'dis_convb_pack_workspace', 'dis_convb_wgrad_workspace', 'dis_colsum_bf16_workspace', 'dis_gn_bwd_workspace', 'dis_act_bwd_ld_bias_workspace', 'dis_conv3d_knn_bwd_workspace', 'dis_geo_loss_acc_doubles', 'dis_geo_loss_multi_acc_doubles', 'dis_masked_l1_multi_acc_doubles', 'dis_conv3d_knn_bwd_det_workspace', 'dis_gather_csr_workspace',
              'dis_conv2d_pack_bf16x3_size', 'dis_disp_head_bwd_workspace', 'dis_geo_loss_bwd_det_workspace',
-             'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_speckle_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace',
+             'dis_adam_step_hyper_workspace', 'dis_render_workspace', 'dis_sgm_workspace', 'dis_speckle_workspace', 'dis_disp_densify_workspace', 'dis_flow_workspace', 'dis_fuse_workspace', 'dis_pose_workspace',
              'dis_pose_joint_workspace', 'dis_disp_align_workspace',
              'dis_tsdf_mesh_workspace', 'dis_tsdf_raycast_workspace', 'dis_tsdf_align_workspace'}
 

@@ -2792,6 +2792,36 @@ def speckle_filter(disp, max_size=100, max_diff=1.0, want_debug=False, workspace
     return (out, dbg) if want_debug else out
 
 
+def disp_densify(disp, max_gap=16, min_dirs=6, max_spread=2.0, median=1, want_state=False, workspace=None):
+    """dis_disp_densify: the disparity maps disp (n, 1, H, W) or (n, H, W) with the holes inside one surface filled and a median over the
+    valid pixels -> a new tensor with the shape of disp (include/dis_hip.h, section "disparity densification"; tests/densify_ref.py
+    restates it in numpy and the kernels equal it bit for bit).  Valid pixels are 0 < d < inf and every other element comes out as
+    +0.0.  Fill (max_gap 1 .. 32, 0: off): an invalid pixel takes the lower median of the first valid pixels met within max_gap steps in
+    the 8 directions when at least min_dirs (1 .. 8) of them meet one and the largest and the smallest differ by at most max_spread
+    (in [0, FLT_MAX]).  Median (1 or 2, 0: off): every valid pixel becomes the lower median of the valid pixels of its (2 r + 1)^2
+    window.  want_state: also state (n, H, W) uint8 - 0 invalid, 1 valid in the input, 2 filled.  The input is data: no autograd.
+    At most two launches on the current stream; workspace: an optional uint8 tensor of at least dis_disp_densify_workspace(...) bytes
+    to reuse between calls (and what makes the call capturable without an allocation)."""
+    _chk(disp)
+    if not (disp.dim() == 3 or (disp.dim() == 4 and disp.shape[1] == 1)):
+        raise RuntimeError('disp_densify: disp (n, 1, H, W) or (n, H, W) is expected')
+    n, h, w = int(disp.shape[0]), int(disp.shape[-2]), int(disp.shape[-1])
+    max_gap, min_dirs, max_spread, median = int(max_gap), int(min_dirs), float(max_spread), int(median)
+    need = lib.fn('dis_disp_densify_workspace')(n, h, w)
+    if need < 0:
+        raise lib.DisHipError(f'dis_disp_densify_workspace: unsupported extents n={n} h={h} w={w}')
+    if not (0 <= max_gap <= 32 and 1 <= min_dirs <= 8 and 0 <= median <= 2 and 0 <= max_spread <= 3.4028234663852886e38):
+        # refused before anything is allocated or launched
+        raise lib.DisHipError(f'disp_densify: unsupported configuration max_gap={max_gap} min_dirs={min_dirs} max_spread={max_spread} '
+                              f'median={median}')
+    dev = disp.device
+    workspace = _workspace('disp_densify', need, workspace, dev)
+    out = torch.empty_like(disp)
+    state = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_state else None
+    lib.call('dis_disp_densify', disp, out, state, n, h, w, max_gap, min_dirs, max_spread, median, workspace)
+    return (out, state) if want_state else out
+
+
 def flow_level_sizes(h, w, min_size=8):
     """[(h_0, w_0), (h_1, w_1), ...] of dis_dense_flow's pyramid: a further level while min(h, w) >= 2 min_size at the coarsest; every
     level halves the one before, rounding up"""

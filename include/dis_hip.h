@@ -878,6 +878,35 @@ long dis_speckle_workspace(int n, int h, int w);
 int dis_speckle_filter(const float* disp, float* out, int* label, int* size, int n, int h, int w, int max_size, float max_diff,
                        void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- disparity densification --- */
+
+/* The two stages classical pipelines run after the matcher and the speckle filter (csrc/densify.hip): holes inside one surface are
+ * filled, then a median over the valid pixels removes sub-pixel noise.  tests/densify_ref.py restates it in numpy and the kernels match
+ * it bit for bit: everything is selection and comparison.
+ *   valid      0 < d < inf, the speckle filter's rule; NaN, +-inf, 0 and negative values are invalid.  Every invalid element of out is
+ *              +0.0f.
+ *   fill       max_gap 1 .. 32 (0: off).  From every invalid pixel, s = 1 .. max_gap steps in each of the 8 directions E, W, S, N, SE,
+ *              SW, NE, NW inside the pixel's own image; the first valid pixel met gives the direction's value, a direction that leaves the
+ *              image or meets none gives no value.  With m values in ascending order v[0] <= ... <= v[m - 1] the pixel becomes
+ *              v[(m - 1) / 2] (the lower median) when m >= min_dirs (1 .. 8) and v[m - 1] - v[0] <= max_spread (one fp32 subtraction;
+ *              max_spread in [0, FLT_MAX], FLT_MAX: no gate); otherwise it stays 0.  Only input values are read: a filled pixel is
+ *              never a source.
+ *   median     median_r 1 or 2 (0: off).  Every pixel that is valid after the fill becomes the lower median v[(k - 1) / 2] of the
+ *              k >= 1 valid pixels of its (2 r + 1)^2 window after the fill, the window clipped to the image.  Only the fill's values
+ *              are read.  Invalid pixels stay 0.
+ * With max_gap = 0 and median_r = 0, out is disp with its invalid elements written as +0.0f.
+ * disp, out (n, h, w): DEVICE; every element of out is written.  state (n, h, w) uint8, DEVICE, NULL: not wanted: 0 invalid, 1 valid in
+ * the input, 2 filled; the median does not change it.  out and state must not overlap disp or each other.
+ * workspace: dis_disp_densify_workspace(n, h, w) BYTES (-1: unsupported extents), 16-byte aligned, no initialisation.  One launch per
+ * stage that is on (one when neither is), no allocation, no synchronisation, no atomics: capturable, and two calls on the same input
+ * give the same bits.
+ * Checks, in this order, before anything is launched: NULL disp, out or workspace -> DIS_ERR_NULL; n, h, w <= 0, h or w > 8192,
+ * n h w >= 2^31 -> DIS_ERR_BAD_SHAPE; max_gap outside 0 .. 32, min_dirs outside 1 .. 8, median_r outside 0 .. 2, max_spread negative,
+ * NaN or infinite, a misaligned workspace, overlapping arrays -> DIS_ERR_UNSUPPORTED. */
+long dis_disp_densify_workspace(int n, int h, int w);
+int dis_disp_densify(const float* disp, float* out, unsigned char* state, int n, int h, int w, int max_gap, int min_dirs,
+                     float max_spread, int median_r, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------- dense optical flow -------- */
 
 /* flow_ij for every ordered pair of frames of a track (csrc/flow.hip): what the multi-frame stage reads from flow.npz, for tracks that
